@@ -21,6 +21,14 @@ Beside `value` (device-resident, as the contract asks) the line carries
 The per-kernel HIP-event timing behind `roofline` is taken in the LAST warm-up pass; after
 the timed steps the batch members that have committed oracle checksums
 (tests/golden/checksums_batch.json) are read back and compared (`parity_check`).
+
+`--dump-outputs DIR` writes what the last timed step handed its caller, as float32 .npy
+files: `log_z.npy` (ln Z of every sequence) and the packed bpp triangles of all sequences
+back to back, whole (`bpp_packed.npy`) when they fit DUMP_BPP_BYTES, else a fixed seeded
+sample of them (`bpp_packed_sample.npy`, at the float64 positions in
+`bpp_packed_sample_positions.npy`).  The inputs are seeded, so two builds run with the same
+arguments can be compared output for output.  With N ranks every rank writes its own shard,
+the names suffixed `_rank<r>`.
 """
 import argparse
 import hashlib
@@ -38,6 +46,10 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X spec (/opt/skills/guides/MI355X_MICROARCH.md)
 T_START = time.time()
+# --dump-outputs: bytes of packed bpp (values + positions of a sample) all ranks together, and
+# the seed of the sample (with ln Z and the .npy headers the files stay under 64 MB)
+DUMP_BPP_BYTES = 48 << 20
+DUMP_SEED = 20250101
 
 
 def shard_lpt(costs, world):
@@ -307,6 +319,24 @@ def tree_leg(ctx, torch, dev, stream, seq, contra, reps, f, ref=None):
     return res
 
 
+def dump_outputs(out_dir, d_out, d_logz, world, rank):
+    """--dump-outputs: the caller-visible outputs of the last timed step (see the module doc)"""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    tag = f"_rank{rank}" if world > 1 else ""
+    np.save(os.path.join(out_dir, f"log_z{tag}.npy"), d_logz.cpu().numpy().astype(np.float32))
+    total = d_out.numel()
+    budget = DUMP_BPP_BYTES // world
+    if 4 * total <= budget:
+        np.save(os.path.join(out_dir, f"bpp_packed{tag}.npy"), d_out.cpu().numpy().astype(np.float32))
+        return
+    k = budget // 12  # 4 B per value + 8 B per position
+    pos = np.sort(np.random.default_rng(DUMP_SEED).integers(0, total, size=k, dtype=np.int64))
+    vals = d_out[torch.from_numpy(pos).to(d_out.device)].cpu().numpy().astype(np.float32)
+    np.save(os.path.join(out_dir, f"bpp_packed_sample{tag}.npy"), vals)
+    np.save(os.path.join(out_dir, f"bpp_packed_sample_positions{tag}.npy"), pos.astype(np.float64))
+
+
 def golden_digest(packed):
     """sha256 of the f32 bits with the libm-exp branch (p >= 0.9999) canonicalised, as
     tests/make_golden.py computes it from the oracle."""
@@ -419,7 +449,7 @@ def relaunch_under_torchrun(args):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=1, help="timed steps (passes over the workload), >= 1")
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default="batch10k", choices=["batch10k", "n4096", "n1024"])
     ap.add_argument("--model", default="turner", choices=["turner", "contra"])
@@ -463,7 +493,12 @@ def main():
                          "members are compared with a reference-order pass of the same run (key sets, max |dp|, "
                          "|d ln Z|) instead of by sha256, the per-kernel rooflines of the reference-order kernels "
                          "and the n = 4096 leg are left out")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the outputs of the last timed step to DIR/*.npy (float32; a fixed "
+                         "seeded sample of the packed bpp when it is large): see the module doc")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and not args.rehearse_shard:
         sys.exit(relaunch_under_torchrun(args))
@@ -702,15 +737,7 @@ def main():
                                           st["ms_outside_small"])
             l_main, l_tail, l_small = (st["launches_outside_main"], st["launches_outside_tail"],
                                        st["launches_outside_small"])
-    steps = args.steps
-    if pass_s is not None:
-        # last resort: fewer timed steps than asked for, reported as such
-        fit = int((args.time_budget_s - (time.time() - T_START) - 5.0) / pass_s)
-        fit = max_over_ranks(float(-fit)) * -1.0  # the smallest fit over ranks
-        if fit < steps:
-            steps = max(1, int(fit))
-            notes.append(f"time budget {args.time_budget_s:.0f} s: timed {steps} of the "
-                         f"{args.steps} steps asked for ({pass_s:.1f} s per pass)")
+    steps = args.steps  # exactly: the time budget trims warm-up passes and optional legs, never these
     torch.cuda.synchronize()
     barrier()
     ms_in = ms_out = 0.0
@@ -733,6 +760,9 @@ def main():
     elapsed = max_over_ranks(local_elapsed)
     pass_s = elapsed / max(steps, 1)
     passes_due = 0
+    if args.dump_outputs:
+        # before anything else writes d_out / d_logz (the tree-order leg below reuses them)
+        dump_outputs(args.dump_outputs, d_out, d_logz, world, rank)
 
     # parity, outside the timed region: batch members with committed oracle checksums
     checked = failed = 0
@@ -1031,8 +1061,6 @@ def main():
                     notes.append(f"tree-order leg: {n_f} of {n_c} golden members failed their check")
             else:
                 notes.append("tree-order batch leg skipped: time budget")
-        if steps != args.steps:
-            res["steps_requested"] = args.steps
         if warm_done != args.warmup:
             res["warmup"] = warm_done
             res["warmup_requested"] = args.warmup

@@ -1,15 +1,15 @@
 """CPU suite for SURVEY.md 8f-4 (Durbin pair-HMM): the oracle restatement of
 src/durbin_algo.rs against what the reference's own test asserts and against
-model-independent properties; the constants against the reference's generated file."""
+model-independent properties; the constants against the published values (tests/golden)."""
 import itertools
+import json
 import os
-import re
 
 import numpy as np
 
 import oracle_lib as O
 
-REF = "/root/reference/src/compiled_align_scores.rs"
+CONSTANTS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "align_scores.json")
 
 
 def scores(init=None):
@@ -27,8 +27,8 @@ def pseudo(seq):
 
 def test_transfer_holds_the_compiled_constants():
     """AlignScores::transfer (src/durbin_algo.rs:42-57) against the committed values of
-    src/compiled_align_scores.rs:2-19; compared with the reference file itself when it is
-    there (it is not on the GPU box)."""
+    src/compiled_align_scores.rs:2-19: all 26 of them, bit for bit, against the stored copy
+    tests/golden/align_scores.json."""
     s = scores()
     want = dict(match2match_score=2.50575671, match2insert_score=0.1970448791,
                 insert_extend_score=1.014026583, insert_switch_score=-7.346968782,
@@ -36,16 +36,15 @@ def test_transfer_holds_the_compiled_constants():
     for k, v in want.items():
         assert np.float32(getattr(s, k)) == np.float32(v), k
     assert np.allclose(s.match_scores, s.match_scores.T) and s.match_scores[0, 0] == np.float32(0.5256508867)
-    if os.path.exists(REF):
-        txt = open(REF).read()
-        nums = [np.float32(x) for x in re.findall(r"-?\d+\.\d+", txt)]
-        assert len(nums) == 16 + 4 + 6
-        assert np.array_equal(np.array(nums[:16], np.float32).reshape(4, 4), s.match_scores)
-        assert np.array_equal(np.array(nums[16:20], np.float32), s.insert_scores)
-        order = ["init_match_score", "init_insert_score", "match2match_score",
-                 "match2insert_score", "insert_extend_score", "insert_switch_score"]
-        for k, v in zip(order, nums[20:]):
-            assert np.float32(getattr(s, k)) == v, k
+    ref = json.load(open(CONSTANTS))
+    match = np.array(ref.pop("match_scores"), np.float32)
+    insert = np.array(ref.pop("insert_scores"), np.float32)
+    ref.pop("what")
+    assert match.shape == (4, 4) and insert.shape == (4,) and len(ref) == 6
+    assert np.array_equal(np.asarray(s.match_scores, np.float32), match)
+    assert np.array_equal(np.asarray(s.insert_scores, np.float32), insert)
+    for k, v in ref.items():
+        assert np.float32(getattr(s, k)) == np.float32(v), k
 
 
 def test_reference_range_assertion_on_the_fixture(trnas):
