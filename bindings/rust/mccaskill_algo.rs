@@ -63,6 +63,8 @@ extern "C" {
   fn rnamc_bpp_batch_multi(pool: *mut RnamcPool, n_seqs: u32, bases: *const u8, offsets: *const u64, uses_contra_model: c_int, allows_short_hairpins: c_int, bpp: *mut f32, out_offsets: *const u64, log_partition: *mut f32) -> c_int;
   fn rnamc_fold_scores(ctx: *mut RnamcCtx, bases: *const u8, n: u32, uses_contra_model: c_int, allows_short_hairpins: c_int, hairpin_scores: *mut f32, multibranch_close_scores: *mut f32, accessible_scores: *mut f32, twoloop_scores: *mut TwoloopScore, twoloop_cap: u64, twoloop_count: *mut u64) -> c_int;
   fn rnamc_fold_sums(ctx: *mut RnamcCtx, bases: *const u8, n: u32, uses_contra_model: c_int, allows_short_hairpins: c_int, sums_external: *mut f32, sums_rightmost_basepairs_external: *mut f32, sums_rightmost_basepairs_multibranch: *mut f32, sums_close: *mut f32, sums_accessible: *mut f32, sums_multibranch: *mut f32, sums_1ormore_basepairs: *mut f32) -> c_int;
+  fn rnamc_sample_batch(ctx: *mut RnamcCtx, n_seqs: u32, bases: *const u8, offsets: *const u64, uses_contra_model: c_int, allows_short_hairpins: c_int, n_samples: u32, seed: u64, structs: *mut u8, log_weights: *mut f32, log_partition: *mut f32) -> c_int;
+  fn rnamc_structure_score(params: *const c_void, bases: *const u8, n: u32, dot_bracket: *const c_char, uses_contra_model: c_int, allows_short_hairpins: c_int, log_weight: *mut f64) -> c_int;
 }
 
 // panic with librnamc's own words (the reference panics on the same inputs:
@@ -456,4 +458,61 @@ pub fn fold_sums_device<T: HashIndex>(
     sums_multibranch: rows(&m[5]),
     sums_1ormore_basepairs: rows(&m[6]),
   }
+}
+
+// Boltzmann sampling (no counterpart in the reference crate): n_samples structures of `seq`
+// drawn with probability exp(log_weight) / Z off the reference-order inside sweep, as
+// (dot_bracket, log_weight) pairs, and ln Z.  Sample t is a pure function of (tables, sequence,
+// flags, seed, t).
+pub fn sample_structures(
+  seq: SeqSlice,
+  n_samples: u32,
+  uses_contra_model: bool,
+  allows_short_hairpins: bool,
+  fold_score_sets: &FoldScoreSets,
+  seed: u64,
+) -> (Vec<(String, f32)>, f32) {
+  let n = seq.len();
+  let bases: Vec<u8> = seq.iter().map(|&x| x as u8).collect();
+  let offsets = [0u64, n as u64];
+  let mut rows = vec![0u8; (n * n_samples as usize).max(1)];
+  let mut weights = vec![0f32; (n_samples as usize).max(1)];
+  let mut log_z = 0f32;
+  with_context(fold_score_sets, |ctx| {
+    check(
+      unsafe {
+        rnamc_sample_batch(ctx, 1, bases.as_ptr(), offsets.as_ptr(), uses_contra_model as c_int,
+          allows_short_hairpins as c_int, n_samples, seed, rows.as_mut_ptr(), weights.as_mut_ptr(),
+          &mut log_z)
+      },
+      "rnamc_sample_batch",
+    );
+  });
+  let samples = (0..n_samples as usize)
+    .map(|t| (String::from_utf8_lossy(&rows[t * n..(t + 1) * n]).into_owned(), weights[t]))
+    .collect();
+  (samples, log_z)
+}
+
+// Log Boltzmann weight of one structure in dot-bracket form (host only): the sum of its loop
+// scores, -inf outside the model's structure space; exp(score - ln Z) is its probability.
+pub fn structure_score(
+  seq: SeqSlice,
+  dot_bracket: &str,
+  uses_contra_model: bool,
+  allows_short_hairpins: bool,
+  fold_score_sets: &FoldScoreSets,
+) -> f64 {
+  let params = build_params(fold_score_sets);
+  let bases: Vec<u8> = seq.iter().map(|&x| x as u8).collect();
+  let db = std::ffi::CString::new(dot_bracket).unwrap();
+  let mut w = 0f64;
+  check(
+    unsafe {
+      rnamc_structure_score(params.as_ptr() as *const c_void, bases.as_ptr(), bases.len() as u32,
+        db.as_ptr(), uses_contra_model as c_int, allows_short_hairpins as c_int, &mut w)
+    },
+    "rnamc_structure_score",
+  );
+  w
 }

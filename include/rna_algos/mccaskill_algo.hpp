@@ -15,6 +15,7 @@
 #ifndef RNA_ALGOS_MCCASKILL_ALGO_HPP
 #define RNA_ALGOS_MCCASKILL_ALGO_HPP
 
+#include <algorithm>
 #include <cstdint>
 #include <memory>
 #include <stdexcept>
@@ -238,6 +239,58 @@ std::vector<SparseProbMat<T>> mccaskill_algo_batch(const Context& ctx, const std
   for (size_t s = 0; s < seqs.size(); s++)
     out.push_back(unpack<T>(packed.data() + ooff[s], static_cast<uint32_t>(seqs[s].size())));
   return out;
+}
+
+// Boltzmann sampling (rnamc_sample_batch; no counterpart in the reference): n_samples structures
+// per sequence, each drawn with probability exp(log_weight) / exp(log_partition).  Sample t of
+// sequence s is a pure function of (tables, sequence, flags, seed, s, t).
+struct SampledStructure {
+  std::string dot_bracket;
+  Score log_weight = 0.f;
+};
+struct SampleSet {
+  std::vector<std::vector<SampledStructure>> samples;  // [sequence][sample]
+  std::vector<Score> log_partition;                     // sums_external[0][n-1] per sequence
+};
+inline SampleSet sample_structures_batch(const Context& ctx, const std::vector<Seq>& seqs,
+                                         uint32_t n_samples, bool uses_contra_model,
+                                         bool allows_short_hairpins, uint64_t seed = 0) {
+  std::vector<uint64_t> off(seqs.size() + 1, 0);
+  for (size_t s = 0; s < seqs.size(); s++) off[s + 1] = off[s] + seqs[s].size();
+  std::vector<Base> bases(off.back() ? off.back() : 1);
+  for (size_t s = 0; s < seqs.size(); s++) std::copy(seqs[s].begin(), seqs[s].end(), bases.begin() + off[s]);
+  std::vector<uint8_t> rows(std::max<uint64_t>(off.back() * n_samples, 1));
+  std::vector<float> weights(std::max<size_t>(seqs.size() * n_samples, 1));
+  SampleSet out;
+  out.log_partition.assign(seqs.size(), 0.f);
+  check(rnamc_sample_batch(ctx.get(), static_cast<uint32_t>(seqs.size()), bases.data(), off.data(),
+                           uses_contra_model, allows_short_hairpins, n_samples, seed, rows.data(),
+                           weights.data(), out.log_partition.empty() ? nullptr : out.log_partition.data()));
+  out.samples.resize(seqs.size());
+  for (size_t s = 0; s < seqs.size(); s++) {
+    const size_t n = seqs[s].size();
+    for (uint32_t t = 0; t < n_samples; t++) {
+      const char* r = reinterpret_cast<const char*>(rows.data() + n_samples * off[s] + t * n);
+      out.samples[s].push_back({std::string(r, n), weights[s * n_samples + t]});
+    }
+  }
+  return out;
+}
+inline std::vector<SampledStructure> sample_structures(const Context& ctx, const Seq& seq,
+                                                       uint32_t n_samples, bool uses_contra_model,
+                                                       bool allows_short_hairpins, uint64_t seed = 0) {
+  return std::move(sample_structures_batch(ctx, {seq}, n_samples, uses_contra_model,
+                                           allows_short_hairpins, seed).samples[0]);
+}
+
+// log Boltzmann weight of one structure (rnamc_structure_score, host only): -inf outside the
+// model's structure space
+inline double structure_score(const FoldScoreSets& f, const Seq& seq, const std::string& dot_bracket,
+                              bool uses_contra_model, bool allows_short_hairpins) {
+  double w = 0;
+  check(rnamc_structure_score(f.p.get(), seq.data(), static_cast<uint32_t>(seq.size()),
+                              dot_bracket.c_str(), uses_contra_model, allows_short_hairpins, &w));
+  return w;
 }
 
 // CentroidFold<T>, src/centroid_fold.rs:4-7

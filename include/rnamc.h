@@ -411,6 +411,37 @@ int rnamc_fold_sums(rnamc_ctx* ctx, const uint8_t* bases, uint32_t n, int uses_c
                     float* sums_1ormore_basepairs);
 
 /* ------------------------------------------------------------------------- */
+/* Boltzmann sampling (stochastic traceback of the inside sweep, reference order, whatever the
+ * context's "summation_mode" says): n_samples secondary structures per sequence, each drawn with
+ * probability exp(score) / Z.  At every cell of the inside grammar the sampler picks one term of
+ * the cell's sum with weight exp(term - max) normalised over the terms themselves (DESIGN.md
+ * section 9 lists the grammar).  Randomness: Philox4x32-10 with key = seed and counter =
+ * (decision index, sample t, batch index s, 0), one uniform u = (word 0 >> 8) * 2^-24 per
+ * decision, so a sample is a pure function of the tables, the sequence and flags, seed, s and t
+ * (not of grouping, of the other sequences of the batch, of knobs or of the device).
+ *   bases, offsets  as rnamc_bpp_batch
+ *   structs       per sequence s, n_samples rows of n_s bytes '(' ')' '.', at
+ *                 structs + n_samples * (offsets[s] - offsets[0]); row t at + t * n_s
+ *   log_weights   n_seqs * n_samples f32, [s * n_samples + t] (may be NULL): the sum of the
+ *                 sample's loop scores in f32 (compare rnamc_structure_score)
+ *   log_partition n_seqs f32, sums_external[0][n-1] (may be NULL)
+ * n_samples == 0 writes nothing and returns RNAMC_OK. */
+int rnamc_sample_batch(rnamc_ctx* ctx, uint32_t n_seqs, const uint8_t* bases,
+                       const uint64_t* offsets, int uses_contra_model, int allows_short_hairpins,
+                       uint32_t n_samples, uint64_t seed, uint8_t* structs, float* log_weights,
+                       float* log_partition);
+
+/* Log Boltzmann weight of one structure (host only, no device): the sum of its loop scores in
+ * f64; -inf (status OK) for a well-formed structure outside the model's space (a non-canonical
+ * pair, a pair of span < 5 unless CONTRAfold with allows_short_hairpins, a CONTRAfold hairpin of
+ * more than 30 unpaired bases, a 2-loop of more than 30); RNAMC_ERR_INVALID_ARG for malformed
+ * input (dot_bracket not of length n, characters other than "().", unbalanced brackets).
+ * exp(log_weight - log Z) is the structure's probability. */
+int rnamc_structure_score(const rnamc_params* params, const uint8_t* bases, uint32_t n,
+                          const char* dot_bracket, int uses_contra_model,
+                          int allows_short_hairpins, double* log_weight);
+
+/* ------------------------------------------------------------------------- */
 /* Consumers of the path's output, host side. */
 
 /* centroid_fold (src/centroid_fold.rs:25-105) driven off a packed bpp triangle

@@ -157,6 +157,13 @@ struct rnamc_ctx {
   std::vector<uint8_t> fs_bases;
   std::vector<float> fs_qb;
   int fs_contra = -1, fs_short = -1;
+  // rnamc_sample_batch (grow-only): a group's rows and log-weights, the per-wave stacks of pending
+  // cells, the per-descriptor row offsets
+  uint8_t* sm_rows = nullptr;
+  float* sm_w = nullptr;
+  uint64_t* sm_stack = nullptr;
+  uint64_t* sm_rowoff = nullptr;
+  uint64_t sm_rows_cap = 0, sm_w_cap = 0, sm_stack_cap = 0, sm_rowoff_cap = 0;
 };
 
 namespace {
@@ -183,21 +190,9 @@ uint64_t tri_pad_of(uint32_t n) {
 
 int ensure_hp_init(rnamc_ctx* c, uint32_t max_n) {
   if (c->hp_init_len >= max_n + 1 && c->d_hp_init) return RNAMC_OK;
-  const rnamc_turner_scores& t = c->host_params.turner;
   uint32_t len = std::max<uint32_t>(max_n + 1, 64);
   std::vector<float> hp(len);
-  const uint32_t m = t.min_hairpin_len_extrapolation - 1;
-  for (uint32_t l = 0; l < len; l++) {
-    if (l <= t.max_hairpin_len_extrapolation) {
-      hp[l] = t.hairpin_scores_init[std::min<uint32_t>(l, RNAMC_MAX_LOOP_LEN)];
-    } else {
-      // HAIRPIN_SCORES_INIT[MIN-1] + COEFF * ln(len / (MIN-1)), all f32 (src/utils.rs:181-183)
-      const float ratio = static_cast<float>(l) / static_cast<float>(m);
-      const float lg = logf(ratio);
-      const float scaled = t.coeff_hairpin_len_extrapolation * lg;
-      hp[l] = t.hairpin_scores_init[m] + scaled;
-    }
-  }
+  hp_init_table(c->host_params.turner, len, hp.data());
   if (c->d_hp_init) HIPCHK(hipFree(c->d_hp_init));
   c->d_hp_init = nullptr;
   c->hp_init_len = 0;
@@ -206,6 +201,25 @@ int ensure_hp_init(rnamc_ctx* c, uint32_t max_n) {
   c->hp_init_len = len;
   c->h_hp_init = std::move(hp);
   return RNAMC_OK;
+}
+
+// Grow-only device buffer: `need` bytes at least (an eighth of headroom when it fits).
+hipError_t grow_device(void** p, uint64_t* cap, uint64_t need) {
+  if (*cap >= need && *p) return hipSuccess;
+  if (*p) {
+    (void)hipFree(*p);
+    *p = nullptr;
+    *cap = 0;
+  }
+  const uint64_t want = std::max<uint64_t>(need + need / 8, 4096);
+  hipError_t e = hipMalloc(p, want);
+  if (e != hipSuccess) {  // the headroom is optional
+    e = hipMalloc(p, std::max<uint64_t>(need, 1));
+    if (e == hipSuccess) *cap = std::max<uint64_t>(need, 1);
+    return e;
+  }
+  *cap = want;
+  return hipSuccess;
 }
 
 int ensure_ws(rnamc_ctx* c, uint64_t floats) {
@@ -1496,6 +1510,10 @@ void rnamc_ctx_destroy(rnamc_ctx* c) {
     if (c->d_seqs) (void)hipFree(c->d_seqs);
     if (c->d_tseqs) (void)hipFree(c->d_tseqs);
     if (c->d_tree_tabs) (void)hipFree(c->d_tree_tabs);
+    if (c->sm_rows) (void)hipFree(c->sm_rows);
+    if (c->sm_w) (void)hipFree(c->sm_w);
+    if (c->sm_stack) (void)hipFree(c->sm_stack);
+    if (c->sm_rowoff) (void)hipFree(c->sm_rowoff);
   }
   delete c;
 }
@@ -1652,23 +1670,7 @@ int rnamc_bpp_batch(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* bases, const u
   // The result is never staged whole: group g's triangles sit in st_out[g & 1] while a host
   // thread drains them (copy stream -> pinned bounce chunks -> the caller's buffers) and
   // group g+1 sweeps into the other buffer.
-  auto grow = [&](void** p, uint64_t* cap, uint64_t need) -> hipError_t {
-    if (*cap >= need && *p) return hipSuccess;
-    if (*p) {
-      (void)hipFree(*p);
-      *p = nullptr;
-      *cap = 0;
-    }
-    const uint64_t want = std::max<uint64_t>(need + need / 8, 4096);
-    hipError_t e = hipMalloc(p, want);
-    if (e != hipSuccess) {  // the headroom is optional
-      e = hipMalloc(p, std::max<uint64_t>(need, 1));
-      if (e == hipSuccess) *cap = std::max<uint64_t>(need, 1);
-      return e;
-    }
-    *cap = want;
-    return hipSuccess;
-  };
+  auto grow = grow_device;
   constexpr uint64_t kChunkFloats = 16ull << 20;  // 64 MB bounce chunks
   if (!c->copy_stream) HIPCHK(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
   for (int k = 0; k < 2; k++) {
@@ -1985,6 +1987,143 @@ int rnamc_fold_sums(rnamc_ctx* c, const uint8_t* bases, uint32_t n, int uses_con
     for (uint32_t d = 0; d < n; d++)
       for (uint32_t i = 0; i + d < n; i++) w.out[static_cast<uint64_t>(i) * n + i + d] = packed[x++];
   }
+  return RNAMC_OK;
+}
+
+// Boltzmann sampling: the reference-order inside sweep of every group (inside_only), then per
+// group the sampling kernel (rnamc_sample.hip) on the same stream before the next group reuses the
+// workspace, and its rows and log-weights copied out to the caller.
+int rnamc_sample_batch(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* bases, const uint64_t* offsets,
+                       int uses_contra_model, int allows_short_hairpins, uint32_t n_samples,
+                       uint64_t seed, uint8_t* structs, float* log_weights, float* log_partition) {
+  if (!c || !offsets || (n_seqs && !bases)) return RNAMC_ERR_INVALID_ARG;
+  if (n_seqs == 0) return RNAMC_OK;
+  for (uint32_t s = 0; s < n_seqs; s++) {
+    if (offsets[s + 1] < offsets[s]) return RNAMC_ERR_INVALID_ARG;
+    const uint64_t n = offsets[s + 1] - offsets[s];
+    if (n == 0) return RNAMC_ERR_EMPTY_SEQ;
+    if (n > RNAMC_MAX_SEQ_LEN) return RNAMC_ERR_SEQ_TOO_LONG;
+    for (uint64_t x = offsets[s]; x < offsets[s + 1]; x++)
+      if (bases[x] > 3) return RNAMC_ERR_INVALID_BASE;
+  }
+  if (n_samples == 0) return RNAMC_OK;
+  if (!structs) return RNAMC_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> lock(c->mu);
+  DeviceGuard guard(c->device);
+  if (!guard.ok) return RNAMC_ERR_NO_DEVICE;
+  const bool contra = uses_contra_model != 0;
+  const uint64_t base_lo = offsets[0], base_hi = offsets[n_seqs];
+  std::vector<uint64_t> doff, rowoff;
+  std::vector<uint8_t> h_rows;
+  std::vector<float> h_w;
+  try {  // nothing may throw across the C boundary
+    doff.resize(n_seqs + 1);
+    rowoff.resize(n_seqs);
+  } catch (const std::exception&) {
+    set_last_error("rnamc_sample_batch: no host memory");
+    return RNAMC_ERR_OOM;
+  }
+  for (uint32_t s = 0; s <= n_seqs; s++) doff[s] = offsets[s] - base_lo;
+  int cus = 0;
+  HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
+  HIPCHK(hipStreamSynchronize(c->own_stream));
+  HIPCHK(grow_device(reinterpret_cast<void**>(&c->st_bases), &c->st_bases_cap, base_hi - base_lo));
+  HIPCHK(grow_device(reinterpret_cast<void**>(&c->st_logz), &c->st_logz_cap,
+                     static_cast<uint64_t>(n_seqs) * sizeof(float)));
+  HIPCHK(hipMemcpyAsync(c->st_bases, bases + base_lo, base_hi - base_lo, hipMemcpyHostToDevice,
+                        c->own_stream));
+  // per wave: a stack of the group's longest n + 1 pending cells; waves: enough to fill the chip,
+  // no more than the items, within 1 GB of stacks
+  auto waves_of = [&](uint64_t items, uint32_t gmax) {
+    uint64_t w = std::min<uint64_t>(items, static_cast<uint64_t>(std::max(cus, 1)) * 16);
+    w = std::min<uint64_t>(w, std::max<uint64_t>((1ull << 30) / ((gmax + 1ull) * 8ull), 4));
+    return static_cast<uint32_t>((w + 3) / 4 * 4);
+  };
+  GroupHooks hooks;
+  hooks.before = [&](size_t g, float** out_base) -> int {
+    if (g == 0) {  // every group's descriptors exist now: size the buffers for the largest group
+      uint64_t rows_max = 0, w_max = 0, stack_max = 0;
+      for (size_t h = 0; h + 1 < c->group_begin.size(); h++) {
+        const uint32_t gb = c->group_begin[h], ge = c->group_begin[h + 1];
+        uint64_t r = 0;
+        for (uint32_t x = gb; x < ge; x++) {
+          rowoff[x] = r;
+          r += static_cast<uint64_t>(c->descs[x].n) * n_samples;
+        }
+        const uint64_t items = static_cast<uint64_t>(ge - gb) * n_samples;
+        const uint32_t gmax = c->descs[gb].n;
+        rows_max = std::max(rows_max, r);
+        w_max = std::max(w_max, items);
+        stack_max = std::max<uint64_t>(stack_max, static_cast<uint64_t>(waves_of(items, gmax)) * (gmax + 1ull));
+      }
+      try {
+        h_rows.resize(rows_max);
+        h_w.resize(w_max);
+      } catch (const std::exception&) {
+        set_last_error("rnamc_sample_batch: no host memory for a group's rows");
+        return RNAMC_ERR_OOM;
+      }
+      HIPCHK(grow_device(reinterpret_cast<void**>(&c->sm_rows), &c->sm_rows_cap, rows_max));
+      HIPCHK(grow_device(reinterpret_cast<void**>(&c->sm_w), &c->sm_w_cap, w_max * sizeof(float)));
+      HIPCHK(grow_device(reinterpret_cast<void**>(&c->sm_stack), &c->sm_stack_cap, stack_max * 8ull));
+      HIPCHK(grow_device(reinterpret_cast<void**>(&c->sm_rowoff), &c->sm_rowoff_cap, n_seqs * 8ull));
+      HIPCHK(hipMemcpyAsync(c->sm_rowoff, rowoff.data(), n_seqs * 8ull, hipMemcpyHostToDevice,
+                            c->own_stream));
+    }
+    // the finalize kernel writes the group's (unused) triangles somewhere: one buffer for all
+    const uint64_t need = std::max<uint64_t>(c->group_out_floats[g], 1) * sizeof(float);
+    HIPCHK(grow_device(reinterpret_cast<void**>(&c->st_out[0]), &c->st_out_cap[0], need));
+    *out_base = c->st_out[0];
+    return RNAMC_OK;
+  };
+  hooks.after = [&](size_t, uint32_t first, uint32_t count) -> int {
+    SampleBatch a{};
+    a.seqs = c->d_seqs + first;
+    a.bases = c->st_bases;
+    a.workspace = c->d_ws;
+    a.params = c->d_params;
+    a.hp_init = c->d_hp_init;
+    a.row_off = c->sm_rowoff + first;
+    a.rows = c->sm_rows;
+    a.log_weights = c->sm_w;
+    a.stack = c->sm_stack;
+    a.stack_cap = c->descs[first].n + 1u;
+    a.nseq = count;
+    a.n_samples = n_samples;
+    a.seed = seed;
+    const uint64_t items = static_cast<uint64_t>(count) * n_samples;
+    launch_sample(a, contra, waves_of(items, c->descs[first].n), c->own_stream);
+    c->stats.launches_other++;
+    HIPCHK(hipGetLastError());
+    const uint64_t rows = rowoff[first + count - 1] +
+                          static_cast<uint64_t>(c->descs[first + count - 1].n) * n_samples;
+    HIPCHK(hipMemcpyAsync(h_rows.data(), c->sm_rows, rows, hipMemcpyDeviceToHost, c->own_stream));
+    HIPCHK(hipMemcpyAsync(h_w.data(), c->sm_w, items * sizeof(float), hipMemcpyDeviceToHost,
+                          c->own_stream));
+    HIPCHK(hipStreamSynchronize(c->own_stream));
+    for (uint32_t x = first; x < first + count; x++) {
+      const SeqDesc& sd = c->descs[x];
+      const uint64_t s = sd.batch_idx;
+      std::memcpy(structs + n_samples * (offsets[s] - offsets[0]), h_rows.data() + rowoff[x],
+                  static_cast<size_t>(sd.n) * n_samples);
+      if (log_weights)
+        std::memcpy(log_weights + s * n_samples, h_w.data() + static_cast<uint64_t>(x - first) * n_samples,
+                    n_samples * sizeof(float));
+    }
+    return RNAMC_OK;
+  };
+  c->inside_only = true;  // the reference-order sweep whatever summation_mode says
+  int rc = run_batch_mode(c, n_seqs, c->st_bases, doff.data(), contra, allows_short_hairpins != 0,
+                          nullptr, nullptr, c->st_logz, c->own_stream, &hooks);
+  c->inside_only = false;
+  if (rc) {
+    (void)hipStreamSynchronize(c->own_stream);
+    return rc;
+  }
+  if (log_partition)
+    HIPCHK(hipMemcpyAsync(log_partition, c->st_logz, n_seqs * sizeof(float), hipMemcpyDeviceToHost,
+                          c->own_stream));
+  HIPCHK(hipStreamSynchronize(c->own_stream));
   return RNAMC_OK;
 }
 

@@ -71,6 +71,24 @@ void launch_durbin(const DurbinPair* d_pairs, uint32_t n_pairs, uint32_t max_cel
 void launch_finalize(const DeviceBatch& b, uint32_t nseq, uint32_t max_n, uint32_t dmin_out,
                      hipStream_t st);
 
+// Boltzmann sampling (rnamc_sample.hip): one wave per (sequence, sample) of a group whose
+// reference-order inside sweep is in the workspace
+struct SampleBatch {
+  const SeqDesc* seqs;      // descriptors of this group
+  const uint8_t* bases;     // base codes of the whole batch
+  const float* workspace;   // DP matrices
+  const rnamc_params* params;
+  const float* hp_init;
+  const uint64_t* row_off;  // per descriptor: byte offset of its n_samples rows of n bytes in `rows`
+  uint8_t* rows;            // '(' ')' '.'
+  float* log_weights;       // [descriptor * n_samples + sample]
+  uint64_t* stack;          // n_waves slices of stack_cap pending cells
+  uint32_t stack_cap, nseq, n_samples;
+  uint64_t seed;
+};
+// n_waves a multiple of 4 (256-thread blocks)
+void launch_sample(const SampleBatch& a, bool contra, uint32_t n_waves, hipStream_t st);
+
 // gamma-centroid fold (rnamc_centroid.hip): per threshold g two dense n x n matrices of msz
 // floats at m + g * 2 * msz (row-major, then column-major), row stride ld, zero-initialised
 struct CentroidBatch {

@@ -1,12 +1,14 @@
 // rnamc_host.cpp — host-side plumbing of librnamc.so: status strings, sequence
 // encoding, parameter-set construction (FoldScoreSets::{new,accumulate,transfer}),
-// the seeded synthetic table generator, table-file I/O and the gamma-centroid
-// fold that consumes the GPU bpp matrices.  No device code here.
+// the seeded synthetic table generator, table-file I/O, the gamma-centroid
+// fold that consumes the GPU bpp matrices and the score of a given structure (the
+// loop scorers of rnamc_scoring.h, host instances).  No device code here.
 //
 // Reference interfaces mirrored (paths relative to the reference tree):
 //   src/mccaskill_algo.rs:24-211  impl FoldScoreSets {new, accumulate, transfer}
 //   src/utils.rs:562-577          bytes2seq
 //   src/centroid_fold.rs:25-105   centroid_fold
+#include <algorithm>
 #include <cmath>
 #include <cstddef>
 #include <cstdio>
@@ -17,6 +19,7 @@
 
 #include "../../include/rnamc.h"
 #include "rnamc_internal.h"
+#include "rnamc_scoring.h"
 
 namespace rnamc {
 
@@ -29,6 +32,21 @@ bool is_canonical(int a, int b) {
   return (a == RNAMC_A && b == RNAMC_U) || (a == RNAMC_C && b == RNAMC_G) ||
          (a == RNAMC_G && b == RNAMC_C) || (a == RNAMC_G && b == RNAMC_U) ||
          (a == RNAMC_U && b == RNAMC_A) || (a == RNAMC_U && b == RNAMC_G);
+}
+
+void hp_init_table(const rnamc_turner_scores& t, uint32_t len, float* out) {
+  const uint32_t m = t.min_hairpin_len_extrapolation - 1;
+  for (uint32_t l = 0; l < len; l++) {
+    if (l <= t.max_hairpin_len_extrapolation) {
+      out[l] = t.hairpin_scores_init[std::min<uint32_t>(l, RNAMC_MAX_LOOP_LEN)];
+    } else {
+      // HAIRPIN_SCORES_INIT[MIN-1] + COEFF * ln(len / (MIN-1)), all f32 (src/utils.rs:181-183)
+      const float ratio = static_cast<float>(l) / static_cast<float>(m);
+      const float lg = logf(ratio);
+      const float scaled = t.coeff_hairpin_len_extrapolation * lg;
+      out[l] = t.hairpin_scores_init[m] + scaled;
+    }
+  }
 }
 
 namespace {
@@ -125,6 +143,62 @@ const FieldDesc kFields[] = {
 #undef FLD_C
 
 const char kMagic[8] = {'R', 'N', 'A', 'M', 'C', 'T', 'B', 'L'};
+
+// Loop decomposition of a pair table (pt[q] = partner or -1) in f64 over the f32 loop scores:
+// the structure space and scoring of the inside grammar (oracle/bruteforce.c states the rules).
+// Iterative: each position is scanned by its innermost enclosing loop only, O(n) in all.
+template <class Model>
+double structure_log_weight(const Model& M, const rnamc_params& P, bool contra, bool shorthp,
+                            const uint8_t* s, uint32_t n, const std::vector<int32_t>& pt) {
+  const double ninf = -std::numeric_limits<double>::infinity();
+  // loop closed by (i, j), or the exterior loop with i = -1, j = n
+  auto loop = [&](int64_t i, int64_t j) -> double {
+    uint32_t unp = 0, nb = 0;
+    int64_t bk = -1, bl = -1;
+    double branches = 0;
+    for (int64_t q = i + 1; q < j;) {
+      if (pt[q] > q) {
+        const uint32_t k = static_cast<uint32_t>(q), l = static_cast<uint32_t>(pt[q]);
+        double acc = M.accessible(s, n, k, l);
+        if (contra)
+          acc += static_cast<double>(i < 0 ? P.contra.external_score_basepair
+                                           : P.contra.multibranch_score_basepair);
+        else if (i >= 0)
+          acc += static_cast<double>(P.turner.coeff_num_branches);
+        branches += acc;
+        bk = k, bl = l;
+        nb++;
+        q = l + 1;
+      } else {
+        unp++;
+        q++;
+      }
+    }
+    if (i < 0)  // exterior: every branch's accessible (+ bp) term, unpaired bases (CONTRAfold)
+      return branches + (contra ? static_cast<double>(P.contra.external_score_unpair) * unp : 0.0);
+    const uint32_t a = static_cast<uint32_t>(i), b = static_cast<uint32_t>(j);
+    if (nb == 0) {
+      if (contra && b - a - 1 > RNAMC_MAX_LOOP_LEN) return ninf;
+      return M.hairpin(s, n, a, b);
+    }
+    if (nb == 1) {
+      if (unp > RNAMC_MAX_2LOOP_LEN) return ninf;
+      return M.twoloop(s, a, b, static_cast<uint32_t>(bk), static_cast<uint32_t>(bl));
+    }
+    double sc = static_cast<double>(M.mbclose(s, n, a, b)) + branches;
+    if (contra) sc += static_cast<double>(P.contra.multibranch_score_unpair) * unp;
+    return sc;
+  };
+  double w = loop(-1, n);
+  for (uint32_t i = 0; i < n; i++) {
+    if (pt[i] <= static_cast<int32_t>(i)) continue;
+    const uint32_t j = static_cast<uint32_t>(pt[i]);
+    if (!canonical(s[i], s[j])) return ninf;
+    if (!(contra && shorthp) && j - i + 1 < RNAMC_MIN_SPAN_HAIRPIN_CLOSE) return ninf;
+    w += loop(i, j);
+  }
+  return w;
+}
 
 }  // namespace
 }  // namespace rnamc
@@ -495,6 +569,55 @@ int rnamc_align_scores_transfer(rnamc_align_scores* s) {
   for (int x = 0; x < 4; x++) {
     s->insert_scores[x] = kInsert[x];
     for (int y = 0; y < 4; y++) s->match_scores[x][y] = kMatch[x][y];
+  }
+  return RNAMC_OK;
+}
+
+int rnamc_structure_score(const rnamc_params* params, const uint8_t* bases, uint32_t n,
+                          const char* dot_bracket, int uses_contra_model,
+                          int allows_short_hairpins, double* log_weight) {
+  if (!params || !bases || !dot_bracket || !log_weight) return RNAMC_ERR_INVALID_ARG;
+  if (params->abi_version != RNAMC_ABI_VERSION || params->struct_bytes != sizeof(rnamc_params))
+    return RNAMC_ERR_INVALID_ARG;
+  if (n == 0) return RNAMC_ERR_EMPTY_SEQ;
+  if (n > RNAMC_MAX_SEQ_LEN) return RNAMC_ERR_SEQ_TOO_LONG;
+  for (uint32_t x = 0; x < n; x++)
+    if (bases[x] > 3) return RNAMC_ERR_INVALID_BASE;
+  const rnamc_turner_scores& t = params->turner;
+  if (t.min_hairpin_len_extrapolation < 2 || t.min_hairpin_len_extrapolation - 1 > RNAMC_MAX_LOOP_LEN ||
+      t.max_hairpin_len_extrapolation > RNAMC_MAX_LOOP_LEN || t.num_special_hairpins > RNAMC_MAX_SPECIAL_HAIRPINS)
+    return RNAMC_ERR_INVALID_ARG;
+  std::vector<int32_t> pt;
+  std::vector<uint32_t> open;
+  std::vector<float> hp;
+  try {  // nothing may throw across the C boundary
+    pt.assign(n, -1);
+    open.reserve(n);
+    if (!uses_contra_model) hp.resize(std::max<uint32_t>(n + 1, 64));
+  } catch (...) {
+    set_last_error("rnamc_structure_score: no host memory");
+    return RNAMC_ERR_OOM;
+  }
+  for (uint32_t x = 0; x < n; x++) {
+    const char ch = dot_bracket[x];
+    if (ch == '(') {
+      open.push_back(x);
+    } else if (ch == ')') {
+      if (open.empty()) return RNAMC_ERR_INVALID_ARG;
+      pt[open.back()] = static_cast<int32_t>(x);
+      pt[x] = static_cast<int32_t>(open.back());
+      open.pop_back();
+    } else if (ch != '.') {
+      return RNAMC_ERR_INVALID_ARG;  // (a terminating NUL before n: wrong length)
+    }
+  }
+  if (!open.empty() || dot_bracket[n] != '\0') return RNAMC_ERR_INVALID_ARG;
+  const bool contra = uses_contra_model != 0, shorthp = allows_short_hairpins != 0;
+  if (contra) {
+    *log_weight = structure_log_weight(Contra{params->contra}, *params, true, shorthp, bases, n, pt);
+  } else {
+    hp_init_table(t, static_cast<uint32_t>(hp.size()), hp.data());
+    *log_weight = structure_log_weight(Turner{t, hp.data()}, *params, false, shorthp, bases, n, pt);
   }
   return RNAMC_OK;
 }

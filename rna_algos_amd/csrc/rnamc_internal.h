@@ -14,6 +14,9 @@ namespace rnamc {
 
 void set_last_error(const std::string& msg);
 bool is_canonical(int a, int b);
+// Turner hairpin initiation by loop length 0 .. len-1, extrapolated past
+// max_hairpin_len_extrapolation (src/utils.rs:174-183): the `hp_init` table of the Turner scorer
+void hp_init_table(const rnamc_turner_scores& t, uint32_t len, float* out);
 
 // DP matrices of one sequence inside the workspace.  Every matrix is a packed
 // upper triangle of n(n+1)/2 f32 (padded to a multiple of 64 floats):

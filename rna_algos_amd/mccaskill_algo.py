@@ -257,6 +257,32 @@ class Context:
                                              int(allows_short_hairpins), *[m.ctypes.data for m in mats]))
         return FoldSums(n, dict(zip(FoldSums.FIELDS, mats)))
 
+    def sample_batch(self, seqs, n_samples, uses_contra_model, allows_short_hairpins, seed=0):
+        """Boltzmann sampling (rnamc_sample_batch): n_samples structures per sequence drawn with
+        probability exp(score) / Z off the reference-order inside sweep -> (list of
+        (n_samples, n_s) uint8 arrays of b'(', b')', b'.', log-weights f32[n_seqs, n_samples],
+        log partition f32[n_seqs])."""
+        for s in seqs:
+            if len(s) == 0:
+                raise _lib.RnamcError(_lib.ERR_EMPTY_SEQ)
+        n_samples = int(n_samples)
+        lens = np.array([len(s) for s in seqs], dtype=np.uint64)
+        offsets = np.zeros(len(seqs) + 1, dtype=np.uint64)
+        np.cumsum(lens, out=offsets[1:])
+        bases = np.concatenate([np.asarray(s, dtype=np.uint8) for s in seqs]) if seqs else \
+            np.zeros(0, np.uint8)
+        rows = np.empty(int(offsets[-1]) * n_samples, dtype=np.uint8)
+        weights = np.empty((len(seqs), n_samples), dtype=np.float32)
+        logz = np.empty(len(seqs), dtype=np.float32)
+        _lib.check(_lib.lib().rnamc_sample_batch(
+            self._h, len(seqs), bases.ctypes.data, offsets.ctypes.data, int(bool(uses_contra_model)),
+            int(bool(allows_short_hairpins)), n_samples, int(seed) & (2**64 - 1),
+            rows.ctypes.data if rows.size else None, weights.ctypes.data if weights.size else None,
+            logz.ctypes.data if logz.size else None))
+        out = [rows[int(offsets[s]) * n_samples:int(offsets[s + 1]) * n_samples].reshape(
+            n_samples, int(lens[s])) for s in range(len(seqs))]
+        return out, weights, logz
+
     def debug_fetch(self, seq_idx, which, n):
         out = np.empty((n, n), dtype=np.float32)
         _lib.check(_lib.lib().rnamc_debug_fetch(self._h, seq_idx, which, out.ctypes.data))
@@ -422,3 +448,41 @@ def mccaskill_algo_batch(seqs, uses_contra_model, allows_short_hairpins, fold_sc
     with _ctx_lock:
         return _pool_for(fold_score_sets).bpp_batch(list(seqs), uses_contra_model,
                                                     allows_short_hairpins)
+
+
+def structure_score(seq, dot_bracket, uses_contra_model, allows_short_hairpins, fold_score_sets):
+    """Log Boltzmann weight of one structure (rnamc_structure_score, host only): the sum of its
+    loop scores; -inf for a structure outside the model's space.  exp(score - ln Z) is its
+    probability."""
+    seq = np.ascontiguousarray(seq, dtype=np.uint8)
+    db = dot_bracket.encode() if isinstance(dot_bracket, str) else bytes(dot_bracket)
+    out = C.c_double()
+    _lib.check(_lib.lib().rnamc_structure_score(fold_score_sets.ptr, seq.ctypes.data,
+                                                int(seq.shape[0]), db, int(bool(uses_contra_model)),
+                                                int(bool(allows_short_hairpins)), C.byref(out)))
+    return out.value
+
+
+def sample_structures_batch(seqs, n_samples, uses_contra_model, allows_short_hairpins,
+                            fold_score_sets, seed=0):
+    """Boltzmann samples of every sequence on the process's shared context -> (per sequence a
+    list of n_samples (dot_bracket, log_weight), log partition f32[n_seqs]).  Sample t of
+    sequence s depends on (tables, sequence, flags, seed, s, t) only."""
+    seqs = [np.asarray(s, dtype=np.uint8) for s in seqs]
+    for s in seqs:
+        if s.shape[0] > MAX_SEQ_LEN:
+            raise _lib.RnamcError(_lib.ERR_SEQ_TOO_LONG)
+    with _ctx_lock:
+        rows, weights, logz = _context_for(fold_score_sets).sample_batch(
+            seqs, n_samples, uses_contra_model, allows_short_hairpins, seed)
+    out = [[(bytes(r).decode(), float(w)) for r, w in zip(m, ws)] for m, ws in zip(rows, weights)]
+    return out, logz
+
+
+def sample_structures(seq, n_samples, uses_contra_model, allows_short_hairpins, fold_score_sets,
+                      seed=0):
+    """n_samples structures of one sequence drawn with probability exp(score) / Z -> (list of
+    (dot_bracket, log_weight), ln Z)."""
+    out, logz = sample_structures_batch([seq], n_samples, uses_contra_model, allows_short_hairpins,
+                                        fold_score_sets, seed)
+    return out[0], float(logz[0])
