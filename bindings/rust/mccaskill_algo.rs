@@ -65,6 +65,7 @@ extern "C" {
   fn rnamc_fold_sums(ctx: *mut RnamcCtx, bases: *const u8, n: u32, uses_contra_model: c_int, allows_short_hairpins: c_int, sums_external: *mut f32, sums_rightmost_basepairs_external: *mut f32, sums_rightmost_basepairs_multibranch: *mut f32, sums_close: *mut f32, sums_accessible: *mut f32, sums_multibranch: *mut f32, sums_1ormore_basepairs: *mut f32) -> c_int;
   fn rnamc_sample_batch(ctx: *mut RnamcCtx, n_seqs: u32, bases: *const u8, offsets: *const u64, uses_contra_model: c_int, allows_short_hairpins: c_int, n_samples: u32, seed: u64, structs: *mut u8, log_weights: *mut f32, log_partition: *mut f32) -> c_int;
   fn rnamc_structure_score(params: *const c_void, bases: *const u8, n: u32, dot_bracket: *const c_char, uses_contra_model: c_int, allows_short_hairpins: c_int, log_weight: *mut f64) -> c_int;
+  fn rnamc_mfe_batch(ctx: *mut RnamcCtx, n_seqs: u32, bases: *const u8, offsets: *const u64, uses_contra_model: c_int, allows_short_hairpins: c_int, structs: *mut u8, scores: *mut f32, dp_scores: *mut f32) -> c_int;
 }
 
 // panic with librnamc's own words (the reference panics on the same inputs:
@@ -515,4 +516,29 @@ pub fn structure_score(
     "rnamc_structure_score",
   );
   w
+}
+
+// Maximum-score structure (no counterpart in the reference crate): MFE under Turner, the Viterbi
+// parse under CONTRAfold, as (dot_bracket, score) with score the f32 sum of its loop scores.
+pub fn mfe_fold(
+  seq: SeqSlice,
+  uses_contra_model: bool,
+  allows_short_hairpins: bool,
+  fold_score_sets: &FoldScoreSets,
+) -> (String, f32) {
+  let n = seq.len();
+  let bases: Vec<u8> = seq.iter().map(|&x| x as u8).collect();
+  let offsets = [0u64, n as u64];
+  let mut row = vec![0u8; n.max(1)];
+  let mut score = 0f32;
+  with_context(fold_score_sets, |ctx| {
+    check(
+      unsafe {
+        rnamc_mfe_batch(ctx, 1, bases.as_ptr(), offsets.as_ptr(), uses_contra_model as c_int,
+          allows_short_hairpins as c_int, row.as_mut_ptr(), &mut score, std::ptr::null_mut())
+      },
+      "rnamc_mfe_batch",
+    );
+  });
+  (String::from_utf8_lossy(&row[..n]).into_owned(), score)
 }

@@ -293,6 +293,37 @@ inline double structure_score(const FoldScoreSets& f, const Seq& seq, const std:
   return w;
 }
 
+// Maximum-score structure (rnamc_mfe_batch; no counterpart in the reference): MFE under Turner,
+// the Viterbi parse under CONTRAfold.  score = the f32 sum of the structure's loop scores (compare
+// structure_score), dp_score = the max-plus sweep's value.
+struct MfeStructure {
+  std::string dot_bracket;
+  Score score = 0.f;
+  Score dp_score = 0.f;
+};
+inline std::vector<MfeStructure> mfe_fold_batch(const Context& ctx, const std::vector<Seq>& seqs,
+                                                bool uses_contra_model, bool allows_short_hairpins) {
+  std::vector<uint64_t> off(seqs.size() + 1, 0);
+  for (size_t s = 0; s < seqs.size(); s++) off[s + 1] = off[s] + seqs[s].size();
+  std::vector<Base> bases(off.back() ? off.back() : 1);
+  for (size_t s = 0; s < seqs.size(); s++) std::copy(seqs[s].begin(), seqs[s].end(), bases.begin() + off[s]);
+  std::vector<uint8_t> rows(std::max<uint64_t>(off.back(), 1));
+  std::vector<float> scores(std::max<size_t>(seqs.size(), 1)), dp(std::max<size_t>(seqs.size(), 1));
+  check(rnamc_mfe_batch(ctx.get(), static_cast<uint32_t>(seqs.size()), bases.data(), off.data(),
+                        uses_contra_model, allows_short_hairpins, rows.data(), scores.data(), dp.data()));
+  std::vector<MfeStructure> out(seqs.size());
+  for (size_t s = 0; s < seqs.size(); s++) {
+    out[s].dot_bracket.assign(reinterpret_cast<const char*>(rows.data() + off[s]), seqs[s].size());
+    out[s].score = scores[s];
+    out[s].dp_score = dp[s];
+  }
+  return out;
+}
+inline MfeStructure mfe_fold(const Context& ctx, const Seq& seq, bool uses_contra_model,
+                             bool allows_short_hairpins) {
+  return std::move(mfe_fold_batch(ctx, {seq}, uses_contra_model, allows_short_hairpins)[0]);
+}
+
 // CentroidFold<T>, src/centroid_fold.rs:4-7
 template <class T>
 struct CentroidFold {

@@ -36,7 +36,9 @@ extern "C" {
 #endif
 
 /* 3: summation_mode knob (tree-order sums), rnamc_ctx_stats (sized copy), multi-device batch
- *    entry rnamc_bpp_batch_multi; rnamc_params itself is unchanged since 2 */
+ *    entry rnamc_bpp_batch_multi; rnamc_params itself is unchanged since 2.  Entries appended
+ *    since, without a version change: rnamc_sample_batch, rnamc_structure_score,
+ *    rnamc_mfe_batch */
 #define RNAMC_ABI_VERSION 3u
 
 /* Compile-time limits.  In the reference these are constants of rna-ss-params
@@ -440,6 +442,20 @@ int rnamc_sample_batch(rnamc_ctx* ctx, uint32_t n_seqs, const uint8_t* bases,
 int rnamc_structure_score(const rnamc_params* params, const uint8_t* bases, uint32_t n,
                           const char* dot_bracket, int uses_contra_model,
                           int allows_short_hairpins, double* log_weight);
+
+/* Maximum-score structure of every sequence (MFE under Turner, Viterbi parse under CONTRAfold):
+ * the inside recurrences in the (max, +) semiring over the structure space that
+ * rnamc_structure_score scores as finite, then an argmax traceback.
+ * Ties: at every cell the first maximal candidate in the sampler's candidate order wins.  The
+ * result depends only on the tables, the sequence and the two flags (not on grouping, the other
+ * sequences of the batch, knobs, summation_mode or the device).
+ *   bases, offsets  as rnamc_bpp_batch
+ *   structs    n_s bytes '(' ')' '.' per sequence at structs + (offsets[s] - offsets[0])
+ *   scores     n_seqs f32: sum of the structure's loop scores (may be NULL)
+ *   dp_scores  n_seqs f32: the max-plus sweep's value (may be NULL) */
+int rnamc_mfe_batch(rnamc_ctx* ctx, uint32_t n_seqs, const uint8_t* bases, const uint64_t* offsets,
+                    int uses_contra_model, int allows_short_hairpins,
+                    uint8_t* structs, float* scores, float* dp_scores);
 
 /* ------------------------------------------------------------------------- */
 /* Consumers of the path's output, host side. */

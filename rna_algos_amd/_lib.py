@@ -29,7 +29,7 @@ SYMBOLS = [
     "rnamc_align_scores_new", "rnamc_align_scores_transfer", "rnamc_durbin_batch",
     "rnamc_pool_create", "rnamc_pool_destroy", "rnamc_pool_size", "rnamc_pool_ctx",
     "rnamc_pool_set_params", "rnamc_pool_set", "rnamc_bpp_batch_multi", "rnamc_shard_plan",
-    "rnamc_sweep_cost", "rnamc_sample_batch", "rnamc_structure_score",
+    "rnamc_sweep_cost", "rnamc_sample_batch", "rnamc_structure_score", "rnamc_mfe_batch",
 ]
 
 
@@ -150,6 +150,7 @@ def lib():
                                      C.c_uint64, vp, vp, vp]
     L.rnamc_structure_score.argtypes = [vp, vp, C.c_uint32, C.c_char_p, C.c_int, C.c_int,
                                         C.POINTER(C.c_double)]
+    L.rnamc_mfe_batch.argtypes = [vp, C.c_uint32, vp, vp, C.c_int, C.c_int, vp, vp, vp]
     _lib = L
     return L
 

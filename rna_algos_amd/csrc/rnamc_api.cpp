@@ -123,6 +123,7 @@ struct rnamc_ctx {
   uint64_t dual_min_cells = 256 * 1024;
   int64_t dual_max_diag = 1 << 30;  // ... while the diagonal has at most this many cells
   bool inside_only = false;  // set by rnamc_fold_scores around its own batch call
+  bool maxplus = false;      // set by rnamc_mfe_batch (with inside_only): the max-plus sweep alone
   int64_t fuse_inside = 1;  // Turner: fold two diagonals per launch where launches are large
   // latency forms (rnamc_latency.h) for groups that cannot fill the chip: 0 never, 1 when the
   // group's longest diagonal holds at most lat_max_cells cells over all its sequences (half of
@@ -164,6 +165,9 @@ struct rnamc_ctx {
   uint64_t* sm_stack = nullptr;
   uint64_t* sm_rowoff = nullptr;
   uint64_t sm_rows_cap = 0, sm_w_cap = 0, sm_stack_cap = 0, sm_rowoff_cap = 0;
+  // rnamc_mfe_batch (grow-only, beside the sampler's buffers): a group's sweep values
+  float* mf_dp = nullptr;
+  uint64_t mf_dp_cap = 0;
 };
 
 namespace {
@@ -382,6 +386,21 @@ int run_batch(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* d_bases, const uint6
     if (prof) HIPCHK(hipEventRecord(c->events[4 * g + 0], st));
     launch_init(b, nseq, gmax, st);
     c->stats.launches_other++;
+    if (c->maxplus) {
+      // max-plus sweep (rnamc_mfe_batch): the closing-pair cells of diagonal dmin_in, then per
+      // diagonal d its sums beside the closing-pair cells of d+1; no outside sweep, no finalize
+      launch_mfe_inside(b, contra, gmax, dmin_in, gmax, nseq, st);
+      for (uint32_t d = dmin_in; d < gmax; d++) launch_mfe_inside(b, contra, d, d + 1, gmax, active(d), st);
+      c->stats.launches_inside += gmax - dmin_in + 1;
+      if (prof)
+        for (int e = 1; e <= 3; e++) HIPCHK(hipEventRecord(c->events[4 * g + e], st));
+      HIPCHK(hipGetLastError());
+      if (hooks) {
+        rc = hooks->after(g, gb, nseq);
+        if (rc) return rc;
+      }
+      continue;
+    }
     // Inside sweep.  Dependencies: the closing-pair block of diagonal D is a left fold whose
     // early part (hairpin, 2-loops) needs sums_close of diagonals <= D-2 and whose last term
     // needs the folds of diagonal D-2; the folds of diagonal D need the pair blocks of
@@ -1514,6 +1533,7 @@ void rnamc_ctx_destroy(rnamc_ctx* c) {
     if (c->sm_w) (void)hipFree(c->sm_w);
     if (c->sm_stack) (void)hipFree(c->sm_stack);
     if (c->sm_rowoff) (void)hipFree(c->sm_rowoff);
+    if (c->mf_dp) (void)hipFree(c->mf_dp);
   }
   delete c;
 }
@@ -2123,6 +2143,134 @@ int rnamc_sample_batch(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* bases, cons
   if (log_partition)
     HIPCHK(hipMemcpyAsync(log_partition, c->st_logz, n_seqs * sizeof(float), hipMemcpyDeviceToHost,
                           c->own_stream));
+  HIPCHK(hipStreamSynchronize(c->own_stream));
+  return RNAMC_OK;
+}
+
+// Maximum-score structure: the max-plus inside sweep of every group (maxplus, run_batch), then per
+// group the argmax traceback (rnamc_mfe.hip) on the same stream before the next group reuses the
+// workspace, and its rows and scores copied out to the caller.
+int rnamc_mfe_batch(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* bases, const uint64_t* offsets,
+                    int uses_contra_model, int allows_short_hairpins, uint8_t* structs, float* scores,
+                    float* dp_scores) {
+  if (!c || !offsets || (n_seqs && !bases)) return RNAMC_ERR_INVALID_ARG;
+  if (n_seqs == 0) return RNAMC_OK;
+  for (uint32_t s = 0; s < n_seqs; s++) {
+    if (offsets[s + 1] < offsets[s]) return RNAMC_ERR_INVALID_ARG;
+    const uint64_t n = offsets[s + 1] - offsets[s];
+    if (n == 0) return RNAMC_ERR_EMPTY_SEQ;
+    if (n > RNAMC_MAX_SEQ_LEN) return RNAMC_ERR_SEQ_TOO_LONG;
+    for (uint64_t x = offsets[s]; x < offsets[s + 1]; x++)
+      if (bases[x] > 3) return RNAMC_ERR_INVALID_BASE;
+  }
+  if (!structs) return RNAMC_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> lock(c->mu);
+  DeviceGuard guard(c->device);
+  if (!guard.ok) return RNAMC_ERR_NO_DEVICE;
+  const bool contra = uses_contra_model != 0;
+  const uint64_t base_lo = offsets[0], base_hi = offsets[n_seqs];
+  std::vector<uint64_t> doff, rowoff;
+  std::vector<uint8_t> h_rows;
+  std::vector<float> h_sc, h_dp;
+  try {  // nothing may throw across the C boundary
+    doff.resize(n_seqs + 1);
+    rowoff.resize(n_seqs);
+  } catch (const std::exception&) {
+    set_last_error("rnamc_mfe_batch: no host memory");
+    return RNAMC_ERR_OOM;
+  }
+  for (uint32_t s = 0; s <= n_seqs; s++) doff[s] = offsets[s] - base_lo;
+  int cus = 0;
+  HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
+  HIPCHK(hipStreamSynchronize(c->own_stream));
+  HIPCHK(grow_device(reinterpret_cast<void**>(&c->st_bases), &c->st_bases_cap, base_hi - base_lo));
+  HIPCHK(hipMemcpyAsync(c->st_bases, bases + base_lo, base_hi - base_lo, hipMemcpyHostToDevice,
+                        c->own_stream));
+  // one wave per sequence: enough to fill the chip, no more than the sequences, within 1 GB of
+  // stacks (the group's longest n + 1 pending cells each)
+  auto waves_of = [&](uint64_t items, uint32_t gmax) {
+    uint64_t w = std::min<uint64_t>(items, static_cast<uint64_t>(std::max(cus, 1)) * 16);
+    w = std::min<uint64_t>(w, std::max<uint64_t>((1ull << 30) / ((gmax + 1ull) * 8ull), 4));
+    return static_cast<uint32_t>((w + 3) / 4 * 4);
+  };
+  GroupHooks hooks;
+  hooks.before = [&](size_t g, float**) -> int {
+    if (g != 0) return RNAMC_OK;
+    // every group's descriptors exist now: size the buffers for the largest group
+    uint64_t rows_max = 0, seq_max = 0, stack_max = 0;
+    for (size_t h = 0; h + 1 < c->group_begin.size(); h++) {
+      const uint32_t gb = c->group_begin[h], ge = c->group_begin[h + 1];
+      uint64_t r = 0;
+      for (uint32_t x = gb; x < ge; x++) {
+        rowoff[x] = r;
+        r += c->descs[x].n;
+      }
+      const uint32_t gmax = c->descs[gb].n;
+      rows_max = std::max(rows_max, r);
+      seq_max = std::max<uint64_t>(seq_max, ge - gb);
+      stack_max = std::max<uint64_t>(stack_max, static_cast<uint64_t>(waves_of(ge - gb, gmax)) * (gmax + 1ull));
+    }
+    try {
+      h_rows.resize(rows_max);
+      h_sc.resize(seq_max);
+      h_dp.resize(seq_max);
+    } catch (const std::exception&) {
+      set_last_error("rnamc_mfe_batch: no host memory for a group's rows");
+      return RNAMC_ERR_OOM;
+    }
+    HIPCHK(grow_device(reinterpret_cast<void**>(&c->sm_rows), &c->sm_rows_cap, rows_max));
+    HIPCHK(grow_device(reinterpret_cast<void**>(&c->sm_w), &c->sm_w_cap, seq_max * sizeof(float)));
+    HIPCHK(grow_device(reinterpret_cast<void**>(&c->mf_dp), &c->mf_dp_cap, seq_max * sizeof(float)));
+    HIPCHK(grow_device(reinterpret_cast<void**>(&c->sm_stack), &c->sm_stack_cap, stack_max * 8ull));
+    HIPCHK(grow_device(reinterpret_cast<void**>(&c->sm_rowoff), &c->sm_rowoff_cap, n_seqs * 8ull));
+    HIPCHK(hipMemcpyAsync(c->sm_rowoff, rowoff.data(), n_seqs * 8ull, hipMemcpyHostToDevice,
+                          c->own_stream));
+    return RNAMC_OK;
+  };
+  hooks.after = [&](size_t, uint32_t first, uint32_t count) -> int {
+    SampleBatch a{};
+    a.seqs = c->d_seqs + first;
+    a.bases = c->st_bases;
+    a.workspace = c->d_ws;
+    a.params = c->d_params;
+    a.hp_init = c->d_hp_init;
+    a.row_off = c->sm_rowoff + first;
+    a.rows = c->sm_rows;
+    a.log_weights = c->sm_w;
+    a.dp_scores = c->mf_dp;
+    a.stack = c->sm_stack;
+    a.stack_cap = c->descs[first].n + 1u;
+    a.nseq = count;
+    a.n_samples = 1;
+    launch_mfe_trace(a, contra, waves_of(count, c->descs[first].n), c->own_stream);
+    c->stats.launches_other++;
+    HIPCHK(hipGetLastError());
+    const uint64_t rows = rowoff[first + count - 1] + c->descs[first + count - 1].n;
+    HIPCHK(hipMemcpyAsync(h_rows.data(), c->sm_rows, rows, hipMemcpyDeviceToHost, c->own_stream));
+    HIPCHK(hipMemcpyAsync(h_sc.data(), c->sm_w, count * sizeof(float), hipMemcpyDeviceToHost,
+                          c->own_stream));
+    HIPCHK(hipMemcpyAsync(h_dp.data(), c->mf_dp, count * sizeof(float), hipMemcpyDeviceToHost,
+                          c->own_stream));
+    HIPCHK(hipStreamSynchronize(c->own_stream));
+    for (uint32_t x = first; x < first + count; x++) {
+      const SeqDesc& sd = c->descs[x];
+      const uint64_t s = sd.batch_idx;
+      std::memcpy(structs + (offsets[s] - offsets[0]), h_rows.data() + rowoff[x], sd.n);
+      if (scores) scores[s] = h_sc[x - first];
+      if (dp_scores) dp_scores[s] = h_dp[x - first];
+    }
+    return RNAMC_OK;
+  };
+  c->inside_only = true;  // run_batch whatever summation_mode says
+  c->maxplus = true;
+  int rc = run_batch_mode(c, n_seqs, c->st_bases, doff.data(), contra, allows_short_hairpins != 0,
+                          nullptr, nullptr, nullptr, c->own_stream, &hooks);
+  c->maxplus = false;
+  c->inside_only = false;
+  if (rc) {
+    (void)hipStreamSynchronize(c->own_stream);
+    return rc;
+  }
   HIPCHK(hipStreamSynchronize(c->own_stream));
   return RNAMC_OK;
 }

@@ -85,9 +85,20 @@ struct SampleBatch {
   uint64_t* stack;          // n_waves slices of stack_cap pending cells
   uint32_t stack_cap, nseq, n_samples;
   uint64_t seed;
+  float* dp_scores;         // maximum-score traceback: [descriptor] sums_external[0][n-1] (may be null)
 };
 // n_waves a multiple of 4 (256-thread blocks)
 void launch_sample(const SampleBatch& a, bool contra, uint32_t n_waves, hipStream_t st);
+
+// Maximum-score (MFE / Viterbi) structure (rnamc_mfe.hip).  The max-plus inside sweep writes the
+// matrices the walker reads (rnamc_walk.h) into the group's workspace, k_init's initial values
+// serving as they are: one launch per diagonal d holds the sums of diagonal d (d_sums < max_n) and
+// the closing-pair cells of diagonal d_pair (< max_n), either may be absent.  Needs launch_init.
+void launch_mfe_inside(const DeviceBatch& b, bool contra, uint32_t d_sums, uint32_t d_pair,
+                       uint32_t max_n, uint32_t nseq, hipStream_t st);
+// argmax traceback of a group whose max-plus sweep is in the workspace: one wave per sequence
+// (a.n_samples = 1; a.log_weights receives the structure's score, a.dp_scores the sweep's value)
+void launch_mfe_trace(const SampleBatch& a, bool contra, uint32_t n_waves, hipStream_t st);
 
 // gamma-centroid fold (rnamc_centroid.hip): per threshold g two dense n x n matrices of msz
 // floats at m + g * 2 * msz (row-major, then column-major), row stride ld, zero-initialised

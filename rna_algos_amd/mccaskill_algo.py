@@ -283,6 +283,28 @@ class Context:
             n_samples, int(lens[s])) for s in range(len(seqs))]
         return out, weights, logz
 
+    def mfe_batch(self, seqs, uses_contra_model, allows_short_hairpins):
+        """Maximum-score structure of every sequence (rnamc_mfe_batch: MFE under Turner, the
+        Viterbi parse under CONTRAfold) -> (list of dot-bracket str, scores f32[n_seqs] = the sum
+        of each structure's loop scores, dp_scores f32[n_seqs] = the max-plus sweep's value)."""
+        for s in seqs:
+            if len(s) == 0:
+                raise _lib.RnamcError(_lib.ERR_EMPTY_SEQ)
+        lens = np.array([len(s) for s in seqs], dtype=np.uint64)
+        offsets = np.zeros(len(seqs) + 1, dtype=np.uint64)
+        np.cumsum(lens, out=offsets[1:])
+        bases = np.concatenate([np.asarray(s, dtype=np.uint8) for s in seqs]) if seqs else \
+            np.zeros(0, np.uint8)
+        rows = np.empty(max(int(offsets[-1]), 1), dtype=np.uint8)
+        scores = np.empty(len(seqs), dtype=np.float32)
+        dp = np.empty(len(seqs), dtype=np.float32)
+        _lib.check(_lib.lib().rnamc_mfe_batch(
+            self._h, len(seqs), bases.ctypes.data, offsets.ctypes.data, int(bool(uses_contra_model)),
+            int(bool(allows_short_hairpins)), rows.ctypes.data,
+            scores.ctypes.data if scores.size else None, dp.ctypes.data if dp.size else None))
+        out = [bytes(rows[int(offsets[s]):int(offsets[s + 1])]).decode() for s in range(len(seqs))]
+        return out, scores, dp
+
     def debug_fetch(self, seq_idx, which, n):
         out = np.empty((n, n), dtype=np.float32)
         _lib.check(_lib.lib().rnamc_debug_fetch(self._h, seq_idx, which, out.ctypes.data))
@@ -486,3 +508,22 @@ def sample_structures(seq, n_samples, uses_contra_model, allows_short_hairpins, 
     out, logz = sample_structures_batch([seq], n_samples, uses_contra_model, allows_short_hairpins,
                                         fold_score_sets, seed)
     return out[0], float(logz[0])
+
+
+def mfe_fold_batch(seqs, uses_contra_model, allows_short_hairpins, fold_score_sets):
+    """Maximum-score structure of every sequence on the process's shared context -> (list of
+    (dot_bracket, score)); score is the f32 sum of the structure's loop scores (compare
+    structure_score).  Ties go to the first maximal candidate in the grammar's order."""
+    seqs = [np.asarray(s, dtype=np.uint8) for s in seqs]
+    for s in seqs:
+        if s.shape[0] > MAX_SEQ_LEN:
+            raise _lib.RnamcError(_lib.ERR_SEQ_TOO_LONG)
+    with _ctx_lock:
+        dbs, scores, _ = _context_for(fold_score_sets).mfe_batch(seqs, uses_contra_model,
+                                                                  allows_short_hairpins)
+    return [(db, float(w)) for db, w in zip(dbs, scores)]
+
+
+def mfe_fold(seq, uses_contra_model, allows_short_hairpins, fold_score_sets):
+    """Maximum-score (MFE / Viterbi) structure of one sequence -> (dot_bracket, score)."""
+    return mfe_fold_batch([seq], uses_contra_model, allows_short_hairpins, fold_score_sets)[0]

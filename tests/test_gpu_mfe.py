@@ -1,0 +1,240 @@
+"""Maximum-score structure on the GPU (rnamc_mfe_batch): against the exhaustive maximum over every
+nested structure (host scorer rnamc_structure_score), against an independent f64 restatement
+(mfe_ref), dominance over Boltzmann samples and ln Z, local optimality, bit-identical invariance
+under grouping, order, summation mode and neighbours, edge cases and the public layers."""
+import ctypes as C
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import oracle_lib as O
+from mfe_ref import mfe_ref
+from test_mfe_cpu import nested_structures
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+MODELS = [(False, False), (True, False), (True, True)]  # (contra, allows_short_hairpins)
+CANON = {(0, 3), (3, 0), (1, 2), (2, 1), (2, 3), (3, 2)}
+
+
+@pytest.fixture(scope="module")
+def ctx(params):
+    from rna_algos_amd.mccaskill_algo import Context
+    c = Context(params, device=0)
+    yield c
+    c.close()
+
+
+def sscore(params, seq, db, contra, short):
+    from rna_algos_amd import _lib
+    seq = np.ascontiguousarray(seq, dtype=np.uint8)
+    out = C.c_double()
+    _lib.check(_lib.lib().rnamc_structure_score(params.ptr, seq.ctypes.data, len(seq), db.encode(),
+                                                int(contra), int(short), C.byref(out)))
+    return out.value
+
+
+def pairs_of(db):
+    st, out = [], []
+    for q, ch in enumerate(db):
+        if ch == "(":
+            st.append(q)
+        elif ch == ")":
+            out.append((st.pop(), q))
+        else:
+            assert ch == "."
+    assert not st
+    return sorted(out)
+
+
+def tol(w, db):
+    return 4 * (len(pairs_of(db)) + 1) * float(np.spacing(np.float32(max(1.0, abs(w)))))
+
+
+def mfe(ctx, seqs, contra, short):
+    dbs, sc, dp = ctx.mfe_batch([np.asarray(s, np.uint8) for s in seqs], contra, short)
+    for db, s in zip(dbs, seqs):
+        assert len(db) == len(s)
+        pairs_of(db)
+    return dbs, sc, dp
+
+
+@pytest.mark.parametrize("contra,short", MODELS)
+def test_exhaustive_small(ctx, params, contra, short):
+    seqs = [O.splitmix_seq(8 + (k * 3) % 9, 7700 + k) for k in range(10)]
+    seqs += [np.zeros(9, np.uint8), np.array([1] * 12, np.uint8)]  # no pair possible
+    dbs, sc, dp = mfe(ctx, seqs, contra, short)
+    for seq, db, s, v in zip(seqs, dbs, sc, dp):
+        ws = sorted(((sscore(params, seq, x, contra, short), x) for x in nested_structures(seq)),
+                    reverse=True)
+        best, arg = ws[0]
+        t = tol(best, db)
+        assert abs(float(s) - best) <= t and abs(float(v) - best) <= t, (seq, db, s, v, best)
+        assert abs(sscore(params, seq, db, contra, short) - best) <= t
+        runner = next((w for w, _ in ws[1:] if w < best), -np.inf)
+        if len([1 for w, _ in ws if w == best]) == 1 and runner < best - 2 * t:
+            assert db == arg, (db, arg)
+        if not any((int(seq[i]), int(seq[j])) in CANON for i in range(len(seq)) for j in range(i + 1, len(seq))):
+            assert db == "." * len(seq)
+
+
+@pytest.mark.parametrize("contra,short", MODELS)
+def test_against_restatement(ctx, params, trnas, contra, short):
+    seqs = [np.asarray(s, np.uint8) for _, s in trnas]
+    seqs += [O.splitmix_seq(n, 9100 + n) for n in (60, 100, 150)]
+    dbs, sc, dp = mfe(ctx, seqs, contra, short)
+    for seq, db, s, v in zip(seqs, dbs, sc, dp):
+        m, _ = mfe_ref(params, seq, contra, short)
+        t = tol(m, db)
+        assert abs(float(v) - m) <= t, (len(seq), v, m)
+        assert abs(sscore(params, seq, db, contra, short) - m) <= t, (len(seq), m)
+        assert abs(float(s) - m) <= t
+
+
+def admissible(seq, i, j, contra, short):
+    return (int(seq[i]), int(seq[j])) in CANON and (j - i + 1 >= 5 or (contra and short))
+
+
+@pytest.mark.parametrize("contra,short", MODELS)
+def test_dominance_and_local_optimality(ctx, params, contra, short):
+    for n in (300, 1000):
+        seq = O.splitmix_seq(n, 31337 + n)
+        (db,), (s,), _ = mfe(ctx, [seq], contra, short)
+        s = float(s)
+        t = tol(s, db) + 8 * float(np.spacing(np.float32(max(1.0, abs(s)))))
+        w = sscore(params, seq, db, contra, short)
+        assert abs(w - s) <= t
+        _, lw, logz = ctx.sample_batch([seq], 2000, contra, short, seed=5)
+        assert np.all(lw[0] <= s + t)
+        assert s <= float(logz[0]) + t
+        pt = [-1] * n
+        for i, j in pairs_of(db):
+            pt[i], pt[j] = j, i
+        chars = list(db)
+        for i, j in pairs_of(db):  # removals
+            chars[i] = chars[j] = "."
+            assert sscore(params, seq, "".join(chars), contra, short) <= s + t
+            chars[i], chars[j] = "(", ")"
+        # additions: both ends unpaired in the same loop (no pair of S crosses (i, j))
+        depth = np.zeros(n + 1, np.int64)
+        for q, ch in enumerate(db):
+            depth[q + 1] = depth[q] + (ch == "(") - (ch == ")")
+        checked = 0
+        for i in range(n):
+            if pt[i] >= 0:
+                continue
+            j = i + 1
+            while j < n:
+                if pt[j] > j:  # skip a whole branch of the loop
+                    j = pt[j] + 1
+                    continue
+                if pt[j] >= 0:  # the loop's closing base: no partner beyond
+                    break
+                if admissible(seq, i, j, contra, short):
+                    chars[i], chars[j] = "(", ")"
+                    assert sscore(params, seq, "".join(chars), contra, short) <= s + t, (i, j)
+                    chars[i] = chars[j] = "."
+                    checked += 1
+                j += 1
+        assert checked > 0
+
+
+@pytest.mark.parametrize("contra,short", MODELS)
+def test_invariance_bit_identical(ctx, params, contra, short):
+    from rna_algos_amd.mccaskill_algo import Context
+    rng = np.random.default_rng(4)
+    seqs = [rng.integers(0, 4, int(n)).astype(np.uint8) for n in rng.integers(1, 400, 40)]
+    base = mfe(ctx, seqs, contra, short)
+    again = mfe(ctx, seqs, contra, short)
+    perm = rng.permutation(len(seqs))
+    shuf = mfe(ctx, [seqs[p] for p in perm], contra, short)
+    c1 = Context(params, device=0)
+    try:
+        c1.set("group_max_seqs", 1)
+        one = mfe(c1, seqs, contra, short)
+    finally:
+        c1.close()
+    c2 = Context(params, device=0)
+    try:
+        c2.set("summation_mode", 1)
+        tree = mfe(c2, seqs, contra, short)
+    finally:
+        c2.close()
+    for other in (again, one, tree):
+        assert other[0] == base[0]
+        assert other[1].tobytes() == base[1].tobytes() and other[2].tobytes() == base[2].tobytes()
+    inv = np.argsort(perm)
+    assert [shuf[0][p] for p in inv] == base[0]
+    assert shuf[1][inv].tobytes() == base[1].tobytes() and shuf[2][inv].tobytes() == base[2].tobytes()
+    # mixed lengths 1 .. 600 against each sequence alone
+    lens = [1, 2, 3, 4, 5, 6, 9, 17, 31, 63, 64, 65, 128, 255, 256, 257, 300, 511, 600]
+    mixed = [rng.integers(0, 4, n).astype(np.uint8) for n in lens]
+    dbs, sc, dp = mfe(ctx, mixed, contra, short)
+    for x, s in enumerate(mixed):
+        d1, s1, v1 = mfe(ctx, [s], contra, short)
+        assert d1[0] == dbs[x] and s1.tobytes() == sc[x:x + 1].tobytes() and v1.tobytes() == dp[x:x + 1].tobytes()
+
+
+@pytest.mark.parametrize("contra,short", MODELS)
+def test_edges(ctx, params, contra, short):
+    seqs = [np.array([2, 1, 3, 0][:n], np.uint8) for n in range(1, 5)]
+    dbs, sc, dp = mfe(ctx, seqs, contra, short)
+    for seq, db, s in zip(seqs, dbs, sc):
+        w = sscore(params, seq, "." * len(seq), contra, short)
+        if not (contra and short):
+            assert db == "." * len(seq)
+            assert abs(float(s) - w) <= tol(w, db)
+        else:  # short hairpins: a pair of span 2 .. 4 may beat all dots
+            assert float(s) >= w - tol(w, db)
+    big = O.splitmix_seq(4096, 4096)
+    (db,), (s,), (v,) = mfe(ctx, [big], contra, short)
+    w = sscore(params, big, db, contra, short)
+    assert np.isfinite(w) and np.isfinite(s)
+    assert abs(float(s) - w) <= tol(w, db)
+    assert abs(float(v) - float(s)) <= 2 * tol(w, db)
+
+
+def test_layers(ctx, params, tmp_path):
+    from rna_algos_amd import _lib
+    from rna_algos_amd.mccaskill_algo import mfe_fold, mfe_fold_batch
+    from rna_algos_amd.utils import FoldScoreSets, bytes2seq
+    rng = np.random.default_rng(8)
+    seqs = [rng.integers(0, 4, n).astype(np.uint8) for n in (23, 80, 5, 140)]
+    for contra, short in MODELS:
+        dbs, sc, _ = mfe(ctx, seqs, contra, short)
+        got = mfe_fold_batch(seqs, contra, short, params)
+        assert [g[0] for g in got] == dbs
+        assert np.array_equal(np.array([g[1] for g in got], np.float32), sc)
+        assert mfe_fold(seqs[1], contra, short, params) == (dbs[1], float(sc[1]))
+    # raw ctypes against the Context method
+    bases = np.concatenate(seqs)
+    offs = np.array([0] + list(np.cumsum([len(s) for s in seqs])), np.uint64)
+    rows = np.zeros(int(offs[-1]), np.uint8)
+    sc2 = np.zeros(len(seqs), np.float32)
+    _lib.check(_lib.lib().rnamc_mfe_batch(ctx._h, len(seqs), bases.ctypes.data, offs.ctypes.data, 1, 0,
+                                          rows.ctypes.data, sc2.ctypes.data, None))
+    dbs, sc, _ = mfe(ctx, seqs, True, False)
+    assert bytes(rows).decode() == "".join(dbs) and sc2.tobytes() == sc.tobytes()
+    # CLI: FASTA in, ">{index}" then "dot_bracket<TAB>score" per record
+    letters = "ACGU"
+    fa = tmp_path / "in.fa"
+    fa.write_text("".join(f">r{x}\n{''.join(letters[b] for b in s)}\n" for x, s in enumerate(seqs)))
+    out = tmp_path / "out.txt"
+    r = subprocess.run([sys.executable, "-m", "rna_algos_amd.bin.mfe_fold", "-i", str(fa), "-o", str(out),
+                        "-c", "--synthetic-tables", "1"], cwd=ROOT, capture_output=True, text=True,
+                       timeout=600)
+    assert r.returncode == 0, r.stderr
+    lines = out.read_text().splitlines()
+    assert len(lines) == 2 * len(seqs)
+    tables = FoldScoreSets.new(0.0)  # what the CLI folds with: the synthetic set, transferred
+    tables.transfer(FoldScoreSets.synthetic(1))
+    ref = mfe_fold_batch([bytes2seq(''.join(letters[b] for b in s).encode()) for s in seqs], True, False,
+                         tables)
+    for x, (db, w) in enumerate(ref):
+        assert lines[2 * x] == f">{x}"
+        got_db, got_w = lines[2 * x + 1].split("\t")
+        assert got_db == db and abs(float(got_w) - w) <= 1e-5 * max(1.0, abs(w))
