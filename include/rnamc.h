@@ -38,7 +38,9 @@ extern "C" {
 /* 3: summation_mode knob (tree-order sums), rnamc_ctx_stats (sized copy), multi-device batch
  *    entry rnamc_bpp_batch_multi; rnamc_params itself is unchanged since 2.  Entries appended
  *    since, without a version change: rnamc_sample_batch, rnamc_structure_score,
- *    rnamc_mfe_batch */
+ *    rnamc_mfe_batch, rnamc_bpp_batch_constrained, rnamc_bpp_batch_multi_constrained,
+ *    rnamc_sample_batch_constrained, rnamc_mfe_batch_constrained, rnamc_log_partition_batch,
+ *    rnamc_constraint_check */
 #define RNAMC_ABI_VERSION 3u
 
 /* Compile-time limits.  In the reference these are constants of rna-ss-params
@@ -456,6 +458,72 @@ int rnamc_structure_score(const rnamc_params* params, const uint8_t* bases, uint
 int rnamc_mfe_batch(rnamc_ctx* ctx, uint32_t n_seqs, const uint8_t* bases, const uint64_t* offsets,
                     int uses_contra_model, int allows_short_hairpins,
                     uint8_t* structs, float* scores, float* dp_scores);
+
+/* ------------------------------------------------------------------------- */
+/* Hard constraints: fold over a restricted structure space (RNAfold's -C without
+ * --enforceConstraint, and --maxBPspan).  Every entry below takes, after
+ * `offsets`,
+ *   constraints   NULL = no string constraints; else sequence s's string of n_s bytes at
+ *                 constraints + (offsets[s] - offsets[0]) (the layout of `bases`, no terminator)
+ *                 over the characters  . x ( ) < >
+ *   max_bp_span   0 = no limit; else the longest admitted span j - i + 1 of a pair (i, j)
+ *                 (span as in RNAMC_MIN_SPAN_HAIRPIN_CLOSE)
+ * Every rule REMOVES pairs; none forces a base to pair.  A pair (i, j), i < j, may form only if
+ * the model allows it (canonical; span >= RNAMC_MIN_SPAN_HAIRPIN_CLOSE unless CONTRAfold with
+ * allows_short_hairpins) and
+ *   - neither i nor j is 'x';
+ *   - if i or j is an end of a matched constraint pair (a, b) ('(' at a, ')' at b), (i, j) = (a, b);
+ *   - (i, j) crosses no constraint pair (a, b): neither i < a < j < b nor a < i < b < j;
+ *   - '<' at p: p pairs only downstream (p = i); '>' at p: p pairs only upstream (p = j);
+ *   - max_bp_span L > 0: j - i + 1 <= L.
+ * A constraint pair whose bases cannot pair (non-canonical, or span too short) still forbids the
+ * pairs that cross it, and its two bases stay unpaired.  Enforced pairs and '|' are not offered.
+ * RNAMC_ERR_INVALID_ARG, before any device work, for an unbalanced bracket or a byte outside the
+ * set ('|' and a terminating NUL of a string shorter than its sequence included); the record and
+ * position are in rnamc_last_error().  A NULL or all-'.' string with max_bp_span 0 or >= n is the
+ * unconstrained problem: results bit-identical to the plain entries, which are these entries with
+ * constraints = NULL, max_bp_span = 0.  A forbidden pair is absent from every output (bpp -1). */
+
+/* rnamc_bpp_batch / rnamc_bpp_batch_multi over the constrained space (both summation modes);
+ * exp(log_partition) is Z_c, and p(i, j) the pair probability given the constraint. */
+int rnamc_bpp_batch_constrained(rnamc_ctx* ctx, uint32_t n_seqs, const uint8_t* bases,
+                                const uint64_t* offsets, const char* constraints,
+                                uint32_t max_bp_span, int uses_contra_model,
+                                int allows_short_hairpins, float* bpp, const uint64_t* out_offsets,
+                                float* log_partition);
+int rnamc_bpp_batch_multi_constrained(rnamc_pool* pool, uint32_t n_seqs, const uint8_t* bases,
+                                      const uint64_t* offsets, const char* constraints,
+                                      uint32_t max_bp_span, int uses_contra_model,
+                                      int allows_short_hairpins, float* bpp,
+                                      const uint64_t* out_offsets, float* log_partition);
+/* rnamc_sample_batch / rnamc_mfe_batch over the constrained space (same outputs; a sample is a pure
+ * function of the tables, the sequence, its constraint, the flags, seed, s and t). */
+int rnamc_sample_batch_constrained(rnamc_ctx* ctx, uint32_t n_seqs, const uint8_t* bases,
+                                   const uint64_t* offsets, const char* constraints,
+                                   uint32_t max_bp_span, int uses_contra_model,
+                                   int allows_short_hairpins, uint32_t n_samples, uint64_t seed,
+                                   uint8_t* structs, float* log_weights, float* log_partition);
+int rnamc_mfe_batch_constrained(rnamc_ctx* ctx, uint32_t n_seqs, const uint8_t* bases,
+                                const uint64_t* offsets, const char* constraints,
+                                uint32_t max_bp_span, int uses_contra_model,
+                                int allows_short_hairpins, uint8_t* structs, float* scores,
+                                float* dp_scores);
+/* ln Z (constrained or not) of every sequence: the reference-order inside sweep alone, whatever
+ * summation_mode says (no outside sweep).  Equal bit for bit to rnamc_bpp_batch's log_partition in
+ * summation_mode 0.  P(constraint) = exp(ln Z_c - ln Z); with 'x' over a region, the probability
+ * that every base of it is unpaired (its accessibility).
+ *   log_partition  n_seqs f32 */
+int rnamc_log_partition_batch(rnamc_ctx* ctx, uint32_t n_seqs, const uint8_t* bases,
+                              const uint64_t* offsets, const char* constraints,
+                              uint32_t max_bp_span, int uses_contra_model,
+                              int allows_short_hairpins, float* log_partition);
+/* Host only: validate a constraint (a NUL-terminated string of length n; RNAMC_ERR_INVALID_ARG as
+ * above, or when its length is not n) and, if dot_bracket (NUL-terminated, length n, "()." and
+ * balanced; RNAMC_ERR_INVALID_ARG otherwise) is not NULL, set *compatible to 1 when every pair of
+ * that structure satisfies the constraint's rules and the span limit, else 0.  The model's own
+ * rules (canonical pairs, minimum span) are not part of the check. */
+int rnamc_constraint_check(const char* constraint, uint32_t n, uint32_t max_bp_span,
+                           const char* dot_bracket, int* compatible);
 
 /* ------------------------------------------------------------------------- */
 /* Consumers of the path's output, host side. */

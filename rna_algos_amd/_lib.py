@@ -30,6 +30,9 @@ SYMBOLS = [
     "rnamc_pool_create", "rnamc_pool_destroy", "rnamc_pool_size", "rnamc_pool_ctx",
     "rnamc_pool_set_params", "rnamc_pool_set", "rnamc_bpp_batch_multi", "rnamc_shard_plan",
     "rnamc_sweep_cost", "rnamc_sample_batch", "rnamc_structure_score", "rnamc_mfe_batch",
+    "rnamc_bpp_batch_constrained", "rnamc_bpp_batch_multi_constrained",
+    "rnamc_sample_batch_constrained", "rnamc_mfe_batch_constrained", "rnamc_log_partition_batch",
+    "rnamc_constraint_check",
 ]
 
 
@@ -151,6 +154,18 @@ def lib():
     L.rnamc_structure_score.argtypes = [vp, vp, C.c_uint32, C.c_char_p, C.c_int, C.c_int,
                                         C.POINTER(C.c_double)]
     L.rnamc_mfe_batch.argtypes = [vp, C.c_uint32, vp, vp, C.c_int, C.c_int, vp, vp, vp]
+    # hard constraints: (constraint strings, max_bp_span) after the offsets
+    L.rnamc_bpp_batch_constrained.argtypes = [vp, C.c_uint32, vp, vp, C.c_char_p, C.c_uint32, C.c_int,
+                                              C.c_int, vp, vp, vp]
+    L.rnamc_bpp_batch_multi_constrained.argtypes = L.rnamc_bpp_batch_constrained.argtypes
+    L.rnamc_sample_batch_constrained.argtypes = [vp, C.c_uint32, vp, vp, C.c_char_p, C.c_uint32, C.c_int,
+                                                 C.c_int, C.c_uint32, C.c_uint64, vp, vp, vp]
+    L.rnamc_mfe_batch_constrained.argtypes = [vp, C.c_uint32, vp, vp, C.c_char_p, C.c_uint32, C.c_int,
+                                              C.c_int, vp, vp, vp]
+    L.rnamc_log_partition_batch.argtypes = [vp, C.c_uint32, vp, vp, C.c_char_p, C.c_uint32, C.c_int,
+                                            C.c_int, vp]
+    L.rnamc_constraint_check.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_char_p,
+                                         C.POINTER(C.c_int)]
     _lib = L
     return L
 

@@ -1,25 +1,25 @@
-"""Maximum-score structure prediction (no binary of the reference does this): the MFE structure
-under Turner, the Viterbi parse under CONTRAfold.
+"""Accessibility of every window of W bases (no binary of the reference does this): the
+probability that all W bases are unpaired, P = Z_c / Z with 'x' over the window.
 
-    python -m rna_algos_amd.bin.mfe_fold -i FASTA -o OUT [-c] [-s] [--synthetic-tables SEED]
-                                         [--constraints FILE] [--max-bp-span L]
+    python -m rna_algos_amd.bin.accessibility -i FASTA -o OUT -w W [-c] [-s] [--synthetic-tables SEED]
 
-The whole FASTA goes to the GPU as one batch (rnamc_mfe_batch).  Per record the output holds
-`>{index}`, then one line `dot_bracket<TAB>score`, score being the sum of the structure's loop
-scores.  Tables as for the other folding CLIs ($RNAMC_TABLES, or --synthetic-tables).
---constraints / --max-bp-span fold over a restricted structure space (bin/_constraints.py)."""
+Per record one batch of the inside-only sweep (rnamc_log_partition_batch): the unconstrained record
+and one constrained record per window.  The output holds `>{index}`, then one line
+`start<TAB>P(unpaired)` per window (start 0-based, windows start .. start + W - 1; none when the
+record is shorter than W).  Tables as for the other folding CLIs ($RNAMC_TABLES, or
+--synthetic-tables)."""
 import argparse
 import sys
 
-from ..mccaskill_algo import mfe_fold_batch
+from ..mccaskill_algo import unpaired_probability
 from ..utils import FoldScoreSets, NoTablesError, read_fasta, set_default_tables
-from . import _constraints
 
 
 def parse_args(argv=None):
-    ap = argparse.ArgumentParser(prog="mfe_fold")
+    ap = argparse.ArgumentParser(prog="accessibility")
     ap.add_argument("-i", "--input_file_path", required=True)
     ap.add_argument("-o", "--output_file_path", required=True)
+    ap.add_argument("-w", "--window", type=int, required=True, help="window length W (bases)")
     ap.add_argument("-c", "--uses_contra_model", action="store_true")
     ap.add_argument("-s", "--allows_short_hairpins", action="store_true",
                     help="CONTRAfold only: hairpins of fewer than 3 unpaired bases")
@@ -27,9 +27,9 @@ def parse_args(argv=None):
                     help="NOT the reference's parameters: seeded synthetic tables (testing only). "
                          "Without it $RNAMC_TABLES must name a table file dumped from the "
                          "rna-ss-params crate")
-    _constraints.add_args(ap)
     args = ap.parse_args(argv)
-    _constraints.check_span(ap, args)
+    if args.window < 1:
+        ap.error("-w must be >= 1")
     return args
 
 
@@ -46,18 +46,16 @@ def main(argv=None):
     except NoTablesError as e:
         print(f"error: {e}", file=sys.stderr)
         return 2
-    cons = None
-    if args.constraints is not None:
-        try:
-            cons = _constraints.load(args.constraints, recs)
-        except (_constraints.ConstraintFileError, OSError) as e:
-            print(f"error: {e}", file=sys.stderr)
-            return 2
-    folds = mfe_fold_batch([s for _, s in recs], args.uses_contra_model,
-                           args.allows_short_hairpins, fold_score_sets, cons, args.max_bp_span)
+    w = args.window
     buf = []
-    for rna_id, (db, score) in enumerate(folds):
-        buf.append(f">{rna_id}\n{db}\t{score:.6f}\n")
+    for rna_id, (_, seq) in enumerate(recs):
+        buf.append(f">{rna_id}\n")
+        starts = range(len(seq) - w + 1)
+        if len(starts) == 0:
+            continue
+        p = unpaired_probability(seq, [(a, a + w - 1) for a in starts], args.uses_contra_model,
+                                 args.allows_short_hairpins, fold_score_sets)
+        buf.extend(f"{a}\t{float(x):.6f}\n" for a, x in zip(starts, p))
     with open(args.output_file_path, "w") as fh:
         fh.write("".join(buf))
     return 0

@@ -6,7 +6,9 @@ Same flags, same output text: a `# Format = ...` header, then per record
 `\\n\\n>{index}\\n` followed by `i,j,p ` triples (Rust `{}` formatting of the f32).  The
 reference iterates a hash map, so the order of the triples inside a record is
 unspecified there; here it is ascending (i, j).  The whole FASTA goes to the GPU as one
-batch instead of one thread-pool task per record; `-t` is accepted and ignored."""
+batch instead of one thread-pool task per record; `-t` is accepted and ignored.
+`--constraints FILE` / `--max-bp-span L` (not in the reference) give the pair probabilities over a
+restricted structure space (bin/_constraints.py)."""
 import argparse
 import sys
 
@@ -14,6 +16,7 @@ import numpy as np
 
 from ..utils import FoldScoreSets, NoTablesError, read_fasta, set_default_tables
 from ..mccaskill_algo import mccaskill_algo_batch
+from . import _constraints
 
 HEADER = ("# Format = >{RNA sequence id} {line break} {basepairing left nucleotide}, "
           "{basepairing right nucleotide}, {basepairing probability} ...")
@@ -41,7 +44,7 @@ def probs2str(mat):
     return "".join(out)
 
 
-def main(argv=None):
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(prog="mccaskill_algo")
     ap.add_argument("-i", "--input_file_path", required=True)
     ap.add_argument("-o", "--output_file_path", required=True)
@@ -51,7 +54,14 @@ def main(argv=None):
                     help="NOT the reference's parameters: seeded synthetic tables (testing only). "
                          "Without it $RNAMC_TABLES must name a table file dumped from the "
                          "rna-ss-params crate")
+    _constraints.add_args(ap)
     args = ap.parse_args(argv)
+    _constraints.check_span(ap, args)
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
     if args.synthetic_tables is not None:
         set_default_tables(FoldScoreSets.synthetic(args.synthetic_tables))
         print(f"warning: SYNTHETIC scoring tables (seed {args.synthetic_tables}): the output is "
@@ -63,8 +73,15 @@ def main(argv=None):
     except NoTablesError as e:
         print(f"error: {e}", file=sys.stderr)
         return 2
+    cons = None
+    if args.constraints is not None:
+        try:
+            cons = _constraints.load(args.constraints, recs)
+        except (_constraints.ConstraintFileError, OSError) as e:
+            print(f"error: {e}", file=sys.stderr)
+            return 2
     mats, _ = mccaskill_algo_batch([s for _, s in recs], args.uses_contra_model, False,
-                                   fold_score_sets)
+                                   fold_score_sets, cons, args.max_bp_span)
     buf = [HEADER]
     for rna_id, m in enumerate(mats):
         buf.append(f"\n\n>{rna_id}\n")

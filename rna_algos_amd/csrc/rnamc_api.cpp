@@ -168,6 +168,13 @@ struct rnamc_ctx {
   // rnamc_mfe_batch (grow-only, beside the sampler's buffers): a group's sweep values
   float* mf_dp = nullptr;
   uint64_t mf_dp_cap = 0;
+  // hard constraints of the running call, set by the constrained entries around their sweep
+  // (ConsInstall, under mu): the staged words (two per base, laid out like st_bases; grow-only) and what
+  // run_batch / run_batch_tree hand to the kernels -- null = unconstrained
+  int32_t* st_cons = nullptr;
+  uint64_t st_cons_cap = 0;
+  const int32_t* cons = nullptr;
+  uint32_t max_span = 0xffffffffu;
 };
 
 namespace {
@@ -372,6 +379,8 @@ int run_batch(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* d_bases, const uint6
     b.params = c->d_params;
     b.hp_init = c->d_hp_init;
     b.allows_short_hairpins = allows_short ? 1 : 0;
+    b.cons = c->cons;
+    b.max_span = c->max_span;
     b.order_inside = static_cast<int>(c->order_inside);
     b.order_outside = static_cast<int>(c->order_outside);
     // sequences with n > d form a prefix of the group
@@ -1045,6 +1054,8 @@ int run_batch_tree(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* d_bases, const 
 #endif
     b.ring = 2u * band;
     b.lane = lane_mode;
+    b.cons = c->cons;
+    b.max_span = c->max_span;
     auto active = [&](uint32_t d) {  // sequences with n > d form a prefix of the group
       uint32_t lo = 0, hi = nseq;
       while (lo < hi) {
@@ -1416,6 +1427,80 @@ void fold_scores_host(const Model& M, bool contra, bool allows_short, const uint
 }  // namespace
 
 namespace {
+// Hard constraints of one batch call (include/rnamc.h).  prepare() validates
+// and compiles every record on the host, before any device work and before the context's lock: two
+// words per base, laid out like the staged bases (rnamc_scoring.h, pair_allowed).  A call with
+// nothing to constrain (no string or only '.', no span limit below the longest record) is not
+// active: it runs exactly the unconstrained sweep.
+struct ConsCall {
+  std::vector<int32_t> words;
+  uint32_t max_span = 0xffffffffu;
+  bool active = false;
+
+  int prepare(uint32_t n_seqs, const uint64_t* offsets, const char* strings, uint32_t max_bp_span) {
+    uint64_t max_n = 0;
+    for (uint32_t s = 0; s < n_seqs; s++) max_n = std::max<uint64_t>(max_n, offsets[s + 1] - offsets[s]);
+    if (max_bp_span != 0 && max_bp_span < max_n) {
+      active = true;
+      max_span = max_bp_span;
+    }
+    const uint64_t lo = offsets[0], total = offsets[n_seqs] - lo;
+    if (strings)
+      for (uint64_t x = 0; x < total && !active; x++) active = strings[x] != '.';
+    if (!active) return RNAMC_OK;
+    try {  // nothing may throw across the C boundary
+      words.assign(2 * total, -1);  // (no string: every base free, outside every constraint pair)
+    } catch (const std::exception&) {
+      set_last_error("constraints: no host memory");
+      return RNAMC_ERR_OOM;
+    }
+    if (!strings) return RNAMC_OK;
+    for (uint32_t s = 0; s < n_seqs; s++) {
+      const uint64_t off = offsets[s] - lo;
+      uint32_t bad = 0;
+      const char* why = "";
+      int rc = RNAMC_OK;
+      try {
+        rc = compile_constraint(strings + off, static_cast<uint32_t>(offsets[s + 1] - offsets[s]),
+                                words.data() + 2 * off, &bad, &why);
+      } catch (const std::exception&) {
+        set_last_error("constraints: no host memory");
+        return RNAMC_ERR_OOM;
+      }
+      if (rc) {
+        set_last_error("constraint of record " + std::to_string(s) + ", position " + std::to_string(bad) +
+                       ": " + why);
+        return rc;
+      }
+    }
+    return RNAMC_OK;
+  }
+};
+
+// Hands a prepared ConsCall to run_batch / run_batch_tree through the context (c->cons,
+// c->max_span) and takes it back when it goes.  The fields belong to the call holding c->mu: each
+// entry constructs this right after its lock_guard, so it is destroyed -- and the fields cleared --
+// while the lock is still held.
+struct ConsInstall {
+  rnamc_ctx* c = nullptr;
+  // (the context's earlier work finished)
+  int install(rnamc_ctx* ctx, const ConsCall& cc, hipStream_t st) {
+    if (!cc.active) return RNAMC_OK;
+    HIPCHK(grow_device(reinterpret_cast<void**>(&ctx->st_cons), &ctx->st_cons_cap, cc.words.size() * sizeof(int32_t)));
+    HIPCHK(hipMemcpyAsync(ctx->st_cons, cc.words.data(), cc.words.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    c = ctx;
+    c->cons = c->st_cons;
+    c->max_span = cc.max_span;
+    return RNAMC_OK;
+  }
+  ~ConsInstall() {
+    if (c) {
+      c->cons = nullptr;
+      c->max_span = 0xffffffffu;
+    }
+  }
+};
+
 int validate_params(const rnamc_params* params) {
   if (params->abi_version != RNAMC_ABI_VERSION || params->struct_bytes != sizeof(rnamc_params)) {
     set_last_error("rnamc_params header does not match this library's ABI");
@@ -1534,6 +1619,7 @@ void rnamc_ctx_destroy(rnamc_ctx* c) {
     if (c->sm_stack) (void)hipFree(c->sm_stack);
     if (c->sm_rowoff) (void)hipFree(c->sm_rowoff);
     if (c->mf_dp) (void)hipFree(c->mf_dp);
+    if (c->st_cons) (void)hipFree(c->st_cons);
   }
   delete c;
 }
@@ -1669,6 +1755,14 @@ int rnamc_bpp_batch_device(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* d_bases
 int rnamc_bpp_batch(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* bases, const uint64_t* offsets,
                     int uses_contra_model, int allows_short_hairpins, float* bpp,
                     const uint64_t* out_offsets, float* log_partition) {
+  return rnamc_bpp_batch_constrained(c, n_seqs, bases, offsets, nullptr, 0, uses_contra_model,
+                                     allows_short_hairpins, bpp, out_offsets, log_partition);
+}
+
+int rnamc_bpp_batch_constrained(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* bases,
+                                const uint64_t* offsets, const char* constraints, uint32_t max_bp_span,
+                                int uses_contra_model, int allows_short_hairpins, float* bpp,
+                                const uint64_t* out_offsets, float* log_partition) {
   if (!c || !offsets || !out_offsets || (n_seqs && (!bases || !bpp))) return RNAMC_ERR_INVALID_ARG;
   if (n_seqs == 0) return RNAMC_OK;
   for (uint32_t s = 0; s < n_seqs; s++) {
@@ -1679,7 +1773,10 @@ int rnamc_bpp_batch(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* bases, const u
     for (uint64_t x = offsets[s]; x < offsets[s + 1]; x++)
       if (bases[x] > 3) return RNAMC_ERR_INVALID_BASE;
   }
+  ConsCall cons;
+  if (int rc = cons.prepare(n_seqs, offsets, constraints, max_bp_span)) return rc;
   std::lock_guard<std::recursive_mutex> lock(c->mu);
+  ConsInstall cons_in;  // (after the lock: cleared before it is released)
   DeviceGuard guard(c->device);
   if (!guard.ok) return RNAMC_ERR_NO_DEVICE;
   const uint64_t base_lo = offsets[0], base_hi = offsets[n_seqs];
@@ -1704,6 +1801,7 @@ int rnamc_bpp_batch(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* bases, const u
               static_cast<uint64_t>(n_seqs) * sizeof(float)));
   HIPCHK(hipMemcpyAsync(c->st_bases, bases + base_lo, base_hi - base_lo, hipMemcpyHostToDevice,
                         c->own_stream));
+  if (int rc = cons_in.install(c, cons, c->own_stream)) return rc;
 
   // drain thread: one job per group, in order
   struct Job {
@@ -2016,6 +2114,16 @@ int rnamc_fold_sums(rnamc_ctx* c, const uint8_t* bases, uint32_t n, int uses_con
 int rnamc_sample_batch(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* bases, const uint64_t* offsets,
                        int uses_contra_model, int allows_short_hairpins, uint32_t n_samples,
                        uint64_t seed, uint8_t* structs, float* log_weights, float* log_partition) {
+  return rnamc_sample_batch_constrained(c, n_seqs, bases, offsets, nullptr, 0, uses_contra_model,
+                                        allows_short_hairpins, n_samples, seed, structs, log_weights,
+                                        log_partition);
+}
+
+int rnamc_sample_batch_constrained(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* bases,
+                                   const uint64_t* offsets, const char* constraints,
+                                   uint32_t max_bp_span, int uses_contra_model,
+                                   int allows_short_hairpins, uint32_t n_samples, uint64_t seed,
+                                   uint8_t* structs, float* log_weights, float* log_partition) {
   if (!c || !offsets || (n_seqs && !bases)) return RNAMC_ERR_INVALID_ARG;
   if (n_seqs == 0) return RNAMC_OK;
   for (uint32_t s = 0; s < n_seqs; s++) {
@@ -2026,9 +2134,12 @@ int rnamc_sample_batch(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* bases, cons
     for (uint64_t x = offsets[s]; x < offsets[s + 1]; x++)
       if (bases[x] > 3) return RNAMC_ERR_INVALID_BASE;
   }
+  ConsCall cons;
+  if (int rc = cons.prepare(n_seqs, offsets, constraints, max_bp_span)) return rc;
   if (n_samples == 0) return RNAMC_OK;
   if (!structs) return RNAMC_ERR_INVALID_ARG;
   std::lock_guard<std::recursive_mutex> lock(c->mu);
+  ConsInstall cons_in;  // (after the lock: cleared before it is released)
   DeviceGuard guard(c->device);
   if (!guard.ok) return RNAMC_ERR_NO_DEVICE;
   const bool contra = uses_contra_model != 0;
@@ -2052,6 +2163,7 @@ int rnamc_sample_batch(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* bases, cons
                      static_cast<uint64_t>(n_seqs) * sizeof(float)));
   HIPCHK(hipMemcpyAsync(c->st_bases, bases + base_lo, base_hi - base_lo, hipMemcpyHostToDevice,
                         c->own_stream));
+  if (int rc = cons_in.install(c, cons, c->own_stream)) return rc;
   // per wave: a stack of the group's longest n + 1 pending cells; waves: enough to fill the chip,
   // no more than the items, within 1 GB of stacks
   auto waves_of = [&](uint64_t items, uint32_t gmax) {
@@ -2147,12 +2259,81 @@ int rnamc_sample_batch(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* bases, cons
   return RNAMC_OK;
 }
 
+// ln Z alone: the reference-order inside sweep of every group (inside_only: no outside sweep) and
+// the finalize kernel that writes sums_external[0][n-1] -- the launches the sampler makes before it
+// samples, so the value is rnamc_bpp_batch's log_partition in summation_mode 0 bit for bit.
+int rnamc_log_partition_batch(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* bases,
+                              const uint64_t* offsets, const char* constraints, uint32_t max_bp_span,
+                              int uses_contra_model, int allows_short_hairpins, float* log_partition) {
+  if (!c || !offsets || (n_seqs && (!bases || !log_partition))) return RNAMC_ERR_INVALID_ARG;
+  if (n_seqs == 0) return RNAMC_OK;
+  for (uint32_t s = 0; s < n_seqs; s++) {
+    if (offsets[s + 1] < offsets[s]) return RNAMC_ERR_INVALID_ARG;
+    const uint64_t n = offsets[s + 1] - offsets[s];
+    if (n == 0) return RNAMC_ERR_EMPTY_SEQ;
+    if (n > RNAMC_MAX_SEQ_LEN) return RNAMC_ERR_SEQ_TOO_LONG;
+    for (uint64_t x = offsets[s]; x < offsets[s + 1]; x++)
+      if (bases[x] > 3) return RNAMC_ERR_INVALID_BASE;
+  }
+  ConsCall cons;
+  if (int rc = cons.prepare(n_seqs, offsets, constraints, max_bp_span)) return rc;
+  std::lock_guard<std::recursive_mutex> lock(c->mu);
+  ConsInstall cons_in;  // (after the lock: cleared before it is released)
+  DeviceGuard guard(c->device);
+  if (!guard.ok) return RNAMC_ERR_NO_DEVICE;
+  const uint64_t base_lo = offsets[0], base_hi = offsets[n_seqs];
+  std::vector<uint64_t> doff;
+  try {  // nothing may throw across the C boundary
+    doff.resize(n_seqs + 1);
+  } catch (const std::exception&) {
+    set_last_error("rnamc_log_partition_batch: no host memory");
+    return RNAMC_ERR_OOM;
+  }
+  for (uint32_t s = 0; s <= n_seqs; s++) doff[s] = offsets[s] - base_lo;
+  HIPCHK(hipStreamSynchronize(c->own_stream));
+  HIPCHK(grow_device(reinterpret_cast<void**>(&c->st_bases), &c->st_bases_cap, base_hi - base_lo));
+  HIPCHK(grow_device(reinterpret_cast<void**>(&c->st_logz), &c->st_logz_cap,
+                     static_cast<uint64_t>(n_seqs) * sizeof(float)));
+  HIPCHK(hipMemcpyAsync(c->st_bases, bases + base_lo, base_hi - base_lo, hipMemcpyHostToDevice,
+                        c->own_stream));
+  if (int rc = cons_in.install(c, cons, c->own_stream)) return rc;
+  GroupHooks hooks;
+  hooks.before = [&](size_t g, float** out_base) -> int {
+    // the finalize kernel writes the group's (unused) triangles somewhere: one buffer for all
+    const uint64_t need = std::max<uint64_t>(c->group_out_floats[g], 1) * sizeof(float);
+    HIPCHK(grow_device(reinterpret_cast<void**>(&c->st_out[0]), &c->st_out_cap[0], need));
+    *out_base = c->st_out[0];
+    return RNAMC_OK;
+  };
+  hooks.after = [](size_t, uint32_t, uint32_t) -> int { return RNAMC_OK; };
+  c->inside_only = true;  // the reference-order sweep whatever summation_mode says
+  int rc = run_batch_mode(c, n_seqs, c->st_bases, doff.data(), uses_contra_model != 0,
+                          allows_short_hairpins != 0, nullptr, nullptr, c->st_logz, c->own_stream, &hooks);
+  c->inside_only = false;
+  if (rc) {
+    (void)hipStreamSynchronize(c->own_stream);
+    return rc;
+  }
+  HIPCHK(hipMemcpyAsync(log_partition, c->st_logz, n_seqs * sizeof(float), hipMemcpyDeviceToHost,
+                        c->own_stream));
+  HIPCHK(hipStreamSynchronize(c->own_stream));
+  return RNAMC_OK;
+}
+
 // Maximum-score structure: the max-plus inside sweep of every group (maxplus, run_batch), then per
 // group the argmax traceback (rnamc_mfe.hip) on the same stream before the next group reuses the
 // workspace, and its rows and scores copied out to the caller.
 int rnamc_mfe_batch(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* bases, const uint64_t* offsets,
                     int uses_contra_model, int allows_short_hairpins, uint8_t* structs, float* scores,
                     float* dp_scores) {
+  return rnamc_mfe_batch_constrained(c, n_seqs, bases, offsets, nullptr, 0, uses_contra_model,
+                                     allows_short_hairpins, structs, scores, dp_scores);
+}
+
+int rnamc_mfe_batch_constrained(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* bases,
+                                const uint64_t* offsets, const char* constraints, uint32_t max_bp_span,
+                                int uses_contra_model, int allows_short_hairpins, uint8_t* structs,
+                                float* scores, float* dp_scores) {
   if (!c || !offsets || (n_seqs && !bases)) return RNAMC_ERR_INVALID_ARG;
   if (n_seqs == 0) return RNAMC_OK;
   for (uint32_t s = 0; s < n_seqs; s++) {
@@ -2164,7 +2345,10 @@ int rnamc_mfe_batch(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* bases, const u
       if (bases[x] > 3) return RNAMC_ERR_INVALID_BASE;
   }
   if (!structs) return RNAMC_ERR_INVALID_ARG;
+  ConsCall cons;
+  if (int rc = cons.prepare(n_seqs, offsets, constraints, max_bp_span)) return rc;
   std::lock_guard<std::recursive_mutex> lock(c->mu);
+  ConsInstall cons_in;  // (after the lock: cleared before it is released)
   DeviceGuard guard(c->device);
   if (!guard.ok) return RNAMC_ERR_NO_DEVICE;
   const bool contra = uses_contra_model != 0;
@@ -2186,6 +2370,7 @@ int rnamc_mfe_batch(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* bases, const u
   HIPCHK(grow_device(reinterpret_cast<void**>(&c->st_bases), &c->st_bases_cap, base_hi - base_lo));
   HIPCHK(hipMemcpyAsync(c->st_bases, bases + base_lo, base_hi - base_lo, hipMemcpyHostToDevice,
                         c->own_stream));
+  if (int rc = cons_in.install(c, cons, c->own_stream)) return rc;
   // one wave per sequence: enough to fill the chip, no more than the sequences, within 1 GB of
   // stacks (the group's longest n + 1 pending cells each)
   auto waves_of = [&](uint64_t items, uint32_t gmax) {

@@ -22,6 +22,10 @@ struct DeviceBatch {
   const float* hp_init;     // Turner hairpin initiation by loop length (host-built)
   int allows_short_hairpins;
   int order_inside, order_outside;  // order in which a launch's role blocks are dispatched
+  // hard constraints (rnamc_scoring.h, pair_allowed): two words per base, laid out like `bases`;
+  // null = unconstrained.  max_span: the longest admitted pair span j - i + 1 where cons is set.
+  const int32_t* cons;
+  uint32_t max_span;
 };
 
 void launch_init(const DeviceBatch& b, uint32_t nseq, uint32_t max_n, hipStream_t st);
@@ -207,6 +211,8 @@ struct TreeBatch {
   int debug;  // timing experiments (builds with -DRNAMC_DEBUG_KNOBS only; 0 otherwise)
   uint32_t ring;  // diagonals the mid-field ring holds (twice the band width; 0: no banding)
   uint32_t lane;  // != 0: both sweeps run lane-per-cell (rnamc_tree_lane.h: statics and sweep matrices diagonal-major)
+  const int32_t* cons;  // hard constraints, as DeviceBatch (read by k_tree_static alone)
+  uint32_t max_span;
 };
 // Launch-shape policy of the tree-order sweep, per context (rnamc_ctx_set "tree_waves",
 // "tree_short", "tree_ahead_waves", "tree_mid_wgs"): passed to every launch, no process globals.

@@ -201,6 +201,47 @@ double structure_log_weight(const Model& M, const rnamc_params& P, bool contra, 
 }
 
 }  // namespace
+int compile_constraint(const char* str, uint32_t n, int32_t* words, uint32_t* bad_pos, const char** why) {
+  // one pass: `open` holds the open brackets; enc(p) is the innermost one open at p (a bracket's own
+  // enc is read before it opens / after it closes: strictly enclosing)
+  std::vector<uint32_t> open;
+  open.reserve(64);
+  for (uint32_t p = 0; p < n; p++) {
+    const char ch = str[p];
+    int32_t rule = kConsFree;
+    if (ch == ')') {
+      if (open.empty()) {
+        *bad_pos = p;
+        *why = "')' without a matching '('";
+        return RNAMC_ERR_INVALID_ARG;
+      }
+      const uint32_t a = open.back();
+      open.pop_back();
+      words[2 * a] = static_cast<int32_t>(p);
+      rule = static_cast<int32_t>(a);
+    } else if (ch == 'x') {
+      rule = kConsNone;
+    } else if (ch == '<') {
+      rule = kConsDown;
+    } else if (ch == '>') {
+      rule = kConsUp;
+    } else if (ch != '.' && ch != '(') {
+      *bad_pos = p;
+      *why = ch == '\0' ? "the string ends before the sequence does" : "character outside \". x ( ) < >\"";
+      return RNAMC_ERR_INVALID_ARG;
+    }
+    words[2 * p] = rule;  // ('(': its partner replaces this once it closes)
+    words[2 * p + 1] = open.empty() ? -1 : static_cast<int32_t>(open.back());
+    if (ch == '(') open.push_back(p);
+  }
+  if (!open.empty()) {
+    *bad_pos = open.back();
+    *why = "'(' without a matching ')'";
+    return RNAMC_ERR_INVALID_ARG;
+  }
+  return RNAMC_OK;
+}
+
 }  // namespace rnamc
 
 using namespace rnamc;
@@ -619,6 +660,64 @@ int rnamc_structure_score(const rnamc_params* params, const uint8_t* bases, uint
     hp_init_table(t, static_cast<uint32_t>(hp.size()), hp.data());
     *log_weight = structure_log_weight(Turner{t, hp.data()}, *params, false, shorthp, bases, n, pt);
   }
+  return RNAMC_OK;
+}
+
+int rnamc_constraint_check(const char* constraint, uint32_t n, uint32_t max_bp_span,
+                           const char* dot_bracket, int* compatible) {
+  if (!constraint || (dot_bracket && !compatible)) {
+    set_last_error(!constraint ? "rnamc_constraint_check: constraint is NULL"
+                               : "rnamc_constraint_check: dot_bracket given without compatible");
+    return RNAMC_ERR_INVALID_ARG;
+  }
+  if (n == 0) return RNAMC_ERR_EMPTY_SEQ;
+  if (n > RNAMC_MAX_SEQ_LEN) return RNAMC_ERR_SEQ_TOO_LONG;
+  std::vector<int32_t> words;
+  std::vector<uint32_t> open;
+  try {  // nothing may throw across the C boundary
+    words.resize(2ull * n);
+    open.reserve(n);
+  } catch (...) {
+    set_last_error("rnamc_constraint_check: no host memory");
+    return RNAMC_ERR_OOM;
+  }
+  uint32_t bad = 0;
+  const char* why = "";
+  if (compile_constraint(constraint, n, words.data(), &bad, &why) != RNAMC_OK) {
+    set_last_error("constraint position " + std::to_string(bad) + ": " + why);
+    return RNAMC_ERR_INVALID_ARG;
+  }
+  if (constraint[n] != '\0') {
+    set_last_error("constraint is longer than n = " + std::to_string(n));
+    return RNAMC_ERR_INVALID_ARG;
+  }
+  if (!dot_bracket) return RNAMC_OK;
+  const uint32_t span = max_bp_span ? max_bp_span : 0xffffffffu;
+  bool ok = true;
+  auto bad_structure = [](uint32_t p, const char* why) {
+    set_last_error("structure position " + std::to_string(p) + ": " + why);
+    return RNAMC_ERR_INVALID_ARG;
+  };
+  for (uint32_t x = 0; x < n; x++) {
+    const char ch = dot_bracket[x];
+    if (ch == '(') {
+      open.push_back(x);
+    } else if (ch == ')') {
+      if (open.empty()) return bad_structure(x, "')' without a matching '('");
+      ok = ok && pair_allowed(words.data(), span, open.back(), x);
+      open.pop_back();
+    } else if (ch == '\0') {
+      return bad_structure(x, "the structure ends before the constraint does");
+    } else if (ch != '.') {
+      return bad_structure(x, "character outside \"( ) .\"");
+    }
+  }
+  if (!open.empty()) return bad_structure(open.back(), "'(' without a matching ')'");
+  if (dot_bracket[n] != '\0') {
+    set_last_error("structure is longer than n = " + std::to_string(n));
+    return RNAMC_ERR_INVALID_ARG;
+  }
+  *compatible = ok ? 1 : 0;
   return RNAMC_OK;
 }
 

@@ -17,6 +17,10 @@ bool is_canonical(int a, int b);
 // Turner hairpin initiation by loop length 0 .. len-1, extrapolated past
 // max_hairpin_len_extrapolation (src/utils.rs:174-183): the `hp_init` table of the Turner scorer
 void hp_init_table(const rnamc_turner_scores& t, uint32_t len, float* out);
+// Hard constraints (include/rnamc.h): the n bytes of a constraint string over
+// ". x ( ) < >" into the 2n words pair_allowed reads (rnamc_scoring.h).  RNAMC_ERR_INVALID_ARG for a
+// byte outside the set or an unbalanced bracket, with its position in *bad_pos and the reason in *why.
+int compile_constraint(const char* str, uint32_t n, int32_t* words, uint32_t* bad_pos, const char** why);
 
 // DP matrices of one sequence inside the workspace.  Every matrix is a packed
 // upper triangle of n(n+1)/2 f32 (padded to a multiple of 64 floats):

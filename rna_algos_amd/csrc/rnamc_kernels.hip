@@ -319,6 +319,7 @@ struct Seq {
   uint32_t* ccnt;
   // c64[w * (n + 64) + D]: canonical cells of diagonal D at positions < 64 w (0 for D >= n)
   uint32_t* c64;
+  const int32_t* cons;  // hard constraints: two words per base (pair_allowed), null = none
 };
 
 __device__ __forceinline__ Seq load_seq(const DeviceBatch& b, uint32_t which) {
@@ -334,6 +335,7 @@ __device__ __forceinline__ Seq load_seq(const DeviceBatch& b, uint32_t which) {
   q.cidx = reinterpret_cast<uint16_t*>(b.workspace + sd.cidx_off);
   q.ccnt = reinterpret_cast<uint32_t*>(b.workspace + sd.ccnt_off);
   q.c64 = reinterpret_cast<uint32_t*>(b.workspace + sd.c64_off);
+  q.cons = b.cons ? b.cons + 2 * sd.seq_off : nullptr;
   return q;
 }
 
@@ -487,6 +489,9 @@ __device__ __forceinline__ void inside_pair_cell(const DeviceBatch& b, const Seq
   const uint8_t* s = q.s;
   bool act = valid && canonical(s[i], s[j]);
   if (!(b.allows_short_hairpins && CONTRA) && d + 1 < RNAMC_MIN_SPAN_HAIRPIN_CLOSE) act = false;
+  // a pair the constraint forbids is treated like one below the minimum span (lanes of a wave hold
+  // different cells: the per-lane flag, ahead of the ballot; b.cons is uniform)
+  if (b.cons && act) act = pair_allowed(q.cons, b.max_span, i, j);
   if (__ballot(act) == 0ull) return;
   const auto model = ModelOf<CONTRA>::make(b);
   const uint32_t o = tri_off(n, d) + i;

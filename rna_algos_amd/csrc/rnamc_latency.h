@@ -576,6 +576,8 @@ __device__ __forceinline__ void inside_pair_lat(const DeviceBatch& b, const Seq&
   const uint8_t* __restrict__ s = q.s;
   const uint32_t lane = threadIdx.x & 63u;
   if (!(b.allows_short_hairpins && CONTRA) && d + 1 < RNAMC_MIN_SPAN_HAIRPIN_CLOSE) return;
+  // a pair the constraint forbids: as above (one wave per listed cell, i is uniform: so is the return)
+  if (b.cons && !pair_allowed(q.cons, b.max_span, i, j)) return;
   const auto model = ModelOf<CONTRA>::make(b);
   const uint32_t o = tri_off(n, d) + i;
   const float* __restrict__ qb = q.m[M_QB];

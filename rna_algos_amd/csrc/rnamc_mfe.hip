@@ -159,9 +159,11 @@ __device__ __forceinline__ void mfe_pair(const DeviceBatch& b, uint32_t seq, uin
   const uint32_t t0 = __builtin_amdgcn_readfirstlane(part * blockDim.x + (tid & ~63u));
   if (t0 >= cnt) return;  // (wave-uniform)
   const uint32_t t = t0 + (tid & 63u);
-  const bool valid = t < cnt;
-  const uint32_t i = cidx[valid ? t : t0];
+  const uint32_t i = cidx[t < cnt ? t : t0];
   const uint32_t j = i + d;
+  // a pair the constraint forbids is treated like one below the minimum span: lanes hold different
+  // cells, so it joins the lane's flag (b.cons is uniform)
+  const bool valid = t < cnt && (!b.cons || pair_allowed(b.cons + 2 * sd.seq_off, b.max_span, i, j));
   float* base = b.workspace + sd.ws_off;
   const uint64_t tp = sd.tri_pad;
   float* __restrict__ qb = base + M_QB * tp;

@@ -156,6 +156,15 @@ int rnamc_bpp_batch_multi(rnamc_pool* p, uint32_t n_seqs, const uint8_t* bases,
                           const uint64_t* offsets, int uses_contra_model,
                           int allows_short_hairpins, float* bpp, const uint64_t* out_offsets,
                           float* log_partition) {
+  return rnamc_bpp_batch_multi_constrained(p, n_seqs, bases, offsets, nullptr, 0, uses_contra_model,
+                                           allows_short_hairpins, bpp, out_offsets, log_partition);
+}
+
+int rnamc_bpp_batch_multi_constrained(rnamc_pool* p, uint32_t n_seqs, const uint8_t* bases,
+                                      const uint64_t* offsets, const char* constraints,
+                                      uint32_t max_bp_span, int uses_contra_model,
+                                      int allows_short_hairpins, float* bpp,
+                                      const uint64_t* out_offsets, float* log_partition) {
   if (!p || p->ctxs.empty() || !offsets || !out_offsets || (n_seqs && (!bases || !bpp)))
     return RNAMC_ERR_INVALID_ARG;
   if (n_seqs == 0) return RNAMC_OK;
@@ -170,6 +179,27 @@ int rnamc_bpp_batch_multi(rnamc_pool* p, uint32_t n_seqs, const uint8_t* bases,
     for (uint64_t x = offsets[s]; x < offsets[s + 1]; x++)
       if (bases[x] > 3) return RNAMC_ERR_INVALID_BASE;
   }
+  if (constraints) {  // (the span limit needs no check)
+    std::vector<int32_t> words;
+    for (uint32_t s = 0; s < n_seqs; s++) {
+      const uint32_t n = static_cast<uint32_t>(offsets[s + 1] - offsets[s]);
+      uint32_t bad = 0;
+      const char* why = "";
+      int rc = RNAMC_OK;
+      try {  // nothing may throw across the C boundary
+        words.resize(2ull * n);
+        rc = rnamc::compile_constraint(constraints + (offsets[s] - offsets[0]), n, words.data(), &bad, &why);
+      } catch (const std::exception&) {
+        rnamc::set_last_error("constraints: no host memory");
+        return RNAMC_ERR_OOM;
+      }
+      if (rc) {
+        rnamc::set_last_error("constraint of record " + std::to_string(s) + ", position " +
+                              std::to_string(bad) + ": " + why);
+        return rc;
+      }
+    }
+  }
   std::lock_guard<std::mutex> lock(p->mu);
   const uint32_t n_shards = static_cast<uint32_t>(std::min<size_t>(p->ctxs.size(), n_seqs));
   std::vector<uint32_t> shard_of(n_seqs), order;
@@ -177,6 +207,7 @@ int rnamc_bpp_batch_multi(rnamc_pool* p, uint32_t n_seqs, const uint8_t* bases,
   struct Shard {
     std::vector<uint32_t> members;  // batch indices, longest first
     std::vector<uint8_t> bases;
+    std::vector<char> cons;  // the members' constraint strings (when the call has them)
     std::vector<uint64_t> offsets, out_offsets;
     std::vector<float> logz;
     int status = RNAMC_OK;
@@ -188,10 +219,12 @@ int rnamc_bpp_batch_multi(rnamc_pool* p, uint32_t n_seqs, const uint8_t* bases,
     uint64_t total = 0;
     for (uint32_t s : sh.members) total += offsets[s + 1] - offsets[s];
     sh.bases.resize(total);
+    if (constraints) sh.cons.resize(total);
     sh.offsets.assign(1, 0);
     for (uint32_t s : sh.members) {
       const uint64_t n = offsets[s + 1] - offsets[s];
       std::memcpy(sh.bases.data() + sh.offsets.back(), bases + offsets[s], n);
+      if (constraints) std::memcpy(sh.cons.data() + sh.offsets.back(), constraints + (offsets[s] - offsets[0]), n);
       sh.offsets.push_back(sh.offsets.back() + n);
       sh.out_offsets.push_back(out_offsets[s]);  // results go straight into the caller's triangles
     }
@@ -201,9 +234,10 @@ int rnamc_bpp_batch_multi(rnamc_pool* p, uint32_t n_seqs, const uint8_t* bases,
   auto work = [&](uint32_t k) {
     Shard& sh = shards[k];
     if (sh.members.empty()) return;
-    sh.status = rnamc_bpp_batch(p->ctxs[k], static_cast<uint32_t>(sh.members.size()), sh.bases.data(),
-                                sh.offsets.data(), uses_contra_model, allows_short_hairpins, bpp,
-                                sh.out_offsets.data(), log_partition ? sh.logz.data() : nullptr);
+    sh.status = rnamc_bpp_batch_constrained(
+        p->ctxs[k], static_cast<uint32_t>(sh.members.size()), sh.bases.data(), sh.offsets.data(),
+        constraints ? sh.cons.data() : nullptr, max_bp_span, uses_contra_model, allows_short_hairpins, bpp,
+        sh.out_offsets.data(), log_partition ? sh.logz.data() : nullptr);
     if (sh.status) sh.error = rnamc_last_error();  // (thread-local: carry it to the caller's thread)
   };
   std::vector<std::thread> pool;

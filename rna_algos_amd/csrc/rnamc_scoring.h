@@ -22,6 +22,28 @@ RNAMC_HD bool canonical(int a, int b) {
   return (a + b == 3) || (a + b == 5);
 }
 
+// Hard constraints (include/rnamc.h).  The host compiles a constraint
+// string into two int32 words per base (compile_constraint, rnamc_host.cpp): the rule word -- the
+// matched partner of a bracket, or one of the codes below -- and enc(p), the opening position of
+// the innermost constraint pair strictly enclosing p (-1: none).
+constexpr int32_t kConsFree = -1;  // '.'
+constexpr int32_t kConsNone = -2;  // 'x': p pairs with nothing
+constexpr int32_t kConsDown = -3;  // '<': p pairs only downstream (p = i)
+constexpr int32_t kConsUp = -4;    // '>': p pairs only upstream (p = j)
+
+// May (i, j), i < j, pair under one sequence's constraint words `cons` and the span limit
+// (max_span: the longest admitted j - i + 1)?  The model's own rule (canonical(), the minimum
+// span) is the caller's.  Two words per end, no loop.  For free i and j, "crosses no constraint
+// pair" is enc(i) == enc(j): the constraint pairs enclosing a position form a chain from enc(p)
+// outwards.  A bracket end pairs with its partner only; brackets are balanced, so that pair
+// crosses no other constraint pair.
+RNAMC_HD bool pair_allowed(const int32_t* cons, uint32_t max_span, uint32_t i, uint32_t j) {
+  const int32_t ri = cons[2 * i], ei = cons[2 * i + 1], rj = cons[2 * j], ej = cons[2 * j + 1];
+  if (j - i + 1u > max_span) return false;
+  if (ri >= 0 || rj >= 0) return ri == static_cast<int32_t>(j);
+  return (ri == kConsFree || ri == kConsDown) && (rj == kConsFree || rj == kConsUp) && ei == ej;
+}
+
 RNAMC_HD bool augu(int a, int b) {
   // AU UA GU UG: canonical and not CG/GC
   return canonical(a, b) && !((a == 1 && b == 2) || (a == 2 && b == 1));

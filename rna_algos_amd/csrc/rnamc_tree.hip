@@ -502,6 +502,8 @@ __global__ void __launch_bounds__(256) k_tree_static(TreeBatch b) {
   const uint32_t n = q.n, ld = q.ld;
   const uint8_t* __restrict__ s = q.s;
   const auto model = TModel<CONTRA>::make(b);
+  // hard constraints: this sequence's words (pair_allowed), laid out like its bases
+  const int32_t* cons = b.cons ? b.cons + 2 * (s - b.bases) : nullptr;
   // row-major statics: x = i n + j; diagonal-major (lane-per-cell sweeps): x = d ld + i, so that a wave's
   // stores are consecutive, and MBC is written for EVERY cell (k_tree_init leaves the statics alone there)
   const uint64_t cells = static_cast<uint64_t>(n) * (b.lane ? ld : n);
@@ -525,8 +527,10 @@ __global__ void __launch_bounds__(256) k_tree_static(TreeBatch b) {
     }
     const uint32_t d = j - i;
     const int si = s[i], sj = s[j];
+    // (T_MBC = -inf is the sweeps' "may not pair": a pair the constraint forbids is one more such cell)
     const bool act = canonical(si, sj) &&
-                     ((b.allows_short_hairpins && CONTRA) || d + 1 >= RNAMC_MIN_SPAN_HAIRPIN_CLOSE);
+                     ((b.allows_short_hairpins && CONTRA) || d + 1 >= RNAMC_MIN_SPAN_HAIRPIN_CLOSE) &&
+                     (!cons || pair_allowed(cons, b.max_span, i, j));
     const size_t o = b.lane ? static_cast<size_t>(d) * ld + i : static_cast<size_t>(i) * ld + j;
     if (!act) {  // (row-major: the slots were filled with -inf / 0 by k_tree_init)
       if (b.lane) q.m[T_MBC][o] = kNegInf;

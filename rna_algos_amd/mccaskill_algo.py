@@ -28,6 +28,52 @@ def bpp_index(n, i, j):
     return d * n - d * (d - 1) // 2 + i
 
 
+def _constraint_bytes(constraints, lens):
+    """Per-record constraint strings (None entries = unconstrained) -> the concatenated bytes the
+    constrained entries read (layout of the bases), or None when no record has one."""
+    if constraints is None:
+        return None
+    constraints = list(constraints)
+    if len(constraints) != len(lens):
+        raise _lib.RnamcError(_lib.ERR_INVALID_ARG,
+                              f"{len(constraints)} constraints for {len(lens)} sequences")
+    if all(c is None for c in constraints):
+        return None
+    parts = []
+    for s, (c, n) in enumerate(zip(constraints, lens)):
+        n = int(n)
+        if c is None:
+            c = b"." * n
+        elif isinstance(c, str):
+            c = c.encode("ascii", errors="replace")
+        else:
+            c = bytes(c)
+        if len(c) != n:
+            raise _lib.RnamcError(_lib.ERR_INVALID_ARG,
+                                  f"constraint of record {s} has length {len(c)}, its sequence {n}")
+        parts.append(c)
+    return b"".join(parts)
+
+
+def _span(max_bp_span):
+    span = int(max_bp_span or 0)
+    if span < 0 or span >= 2 ** 32:
+        raise _lib.RnamcError(_lib.ERR_INVALID_ARG, f"max_bp_span {span} out of range")
+    return span
+
+
+def _pack(seqs):
+    for s in seqs:
+        if len(s) == 0:
+            raise _lib.RnamcError(_lib.ERR_EMPTY_SEQ)
+    lens = np.array([len(s) for s in seqs], dtype=np.uint64)
+    offsets = np.zeros(len(seqs) + 1, dtype=np.uint64)
+    np.cumsum(lens, out=offsets[1:])
+    bases = np.concatenate([np.asarray(s, dtype=np.uint8) for s in seqs]) if seqs else \
+        np.zeros(0, np.uint8)
+    return lens, offsets, bases
+
+
 class BppMatrix:
     """One sequence's result: packed triangle of f32, absent pairs hold -1.0.
     `sparse()` gives the reference's SparseProbMat<T> as a dict {(i, j): p}."""
@@ -183,24 +229,22 @@ class Context:
         _lib.check(_lib.lib().rnamc_ctx_stats(self._h, C.byref(st), C.sizeof(st), None))
         return {k: getattr(st, k) for k, _ in st._fields_}
 
-    def bpp_batch(self, seqs, uses_contra_model, allows_short_hairpins):
-        """seqs: list of np.uint8 code arrays -> (list of BppMatrix, log partition f32[])."""
-        for s in seqs:
-            if len(s) == 0:
-                raise _lib.RnamcError(_lib.ERR_EMPTY_SEQ)
-        lens = np.array([len(s) for s in seqs], dtype=np.uint64)
-        offsets = np.zeros(len(seqs) + 1, dtype=np.uint64)
-        np.cumsum(lens, out=offsets[1:])
-        bases = np.concatenate([np.asarray(s, dtype=np.uint8) for s in seqs]) if seqs else \
-            np.zeros(0, np.uint8)
+    def bpp_batch(self, seqs, uses_contra_model, allows_short_hairpins, constraints=None,
+                  max_bp_span=0):
+        """seqs: list of np.uint8 code arrays -> (list of BppMatrix, log partition f32[]).
+        constraints: None, or one constraint string (". x ( ) < >", None = unconstrained) per
+        sequence; max_bp_span: longest admitted pair span j - i + 1, 0 = no limit
+        (include/rnamc.h, hard constraints)."""
+        lens, offsets, bases = _pack(seqs)
+        cons = _constraint_bytes(constraints, lens)
         out_offsets = np.zeros(len(seqs) + 1, dtype=np.uint64)
         np.cumsum(lens * (lens + 1) // 2, out=out_offsets[1:])
         bpp = np.empty(int(out_offsets[-1]), dtype=np.float32)
         logz = np.empty(len(seqs), dtype=np.float32)
-        _lib.check(_lib.lib().rnamc_bpp_batch(
-            self._h, len(seqs), bases.ctypes.data, offsets.ctypes.data, int(bool(uses_contra_model)),
-            int(bool(allows_short_hairpins)), bpp.ctypes.data, out_offsets.ctypes.data,
-            logz.ctypes.data))
+        _lib.check(_lib.lib().rnamc_bpp_batch_constrained(
+            self._h, len(seqs), bases.ctypes.data, offsets.ctypes.data, cons, _span(max_bp_span),
+            int(bool(uses_contra_model)), int(bool(allows_short_hairpins)), bpp.ctypes.data,
+            out_offsets.ctypes.data, logz.ctypes.data))
         mats = [BppMatrix(int(lens[s]), bpp[int(out_offsets[s]):int(out_offsets[s + 1])])
                 for s in range(len(seqs))]
         return mats, logz
@@ -257,53 +301,58 @@ class Context:
                                              int(allows_short_hairpins), *[m.ctypes.data for m in mats]))
         return FoldSums(n, dict(zip(FoldSums.FIELDS, mats)))
 
-    def sample_batch(self, seqs, n_samples, uses_contra_model, allows_short_hairpins, seed=0):
+    def sample_batch(self, seqs, n_samples, uses_contra_model, allows_short_hairpins, seed=0,
+                     constraints=None, max_bp_span=0):
         """Boltzmann sampling (rnamc_sample_batch): n_samples structures per sequence drawn with
         probability exp(score) / Z off the reference-order inside sweep -> (list of
         (n_samples, n_s) uint8 arrays of b'(', b')', b'.', log-weights f32[n_seqs, n_samples],
-        log partition f32[n_seqs])."""
-        for s in seqs:
-            if len(s) == 0:
-                raise _lib.RnamcError(_lib.ERR_EMPTY_SEQ)
+        log partition f32[n_seqs]).  constraints, max_bp_span: as bpp_batch (then Z is Z_c)."""
         n_samples = int(n_samples)
-        lens = np.array([len(s) for s in seqs], dtype=np.uint64)
-        offsets = np.zeros(len(seqs) + 1, dtype=np.uint64)
-        np.cumsum(lens, out=offsets[1:])
-        bases = np.concatenate([np.asarray(s, dtype=np.uint8) for s in seqs]) if seqs else \
-            np.zeros(0, np.uint8)
+        lens, offsets, bases = _pack(seqs)
+        cons = _constraint_bytes(constraints, lens)
         rows = np.empty(int(offsets[-1]) * n_samples, dtype=np.uint8)
         weights = np.empty((len(seqs), n_samples), dtype=np.float32)
         logz = np.empty(len(seqs), dtype=np.float32)
-        _lib.check(_lib.lib().rnamc_sample_batch(
-            self._h, len(seqs), bases.ctypes.data, offsets.ctypes.data, int(bool(uses_contra_model)),
-            int(bool(allows_short_hairpins)), n_samples, int(seed) & (2**64 - 1),
+        _lib.check(_lib.lib().rnamc_sample_batch_constrained(
+            self._h, len(seqs), bases.ctypes.data, offsets.ctypes.data, cons, _span(max_bp_span),
+            int(bool(uses_contra_model)), int(bool(allows_short_hairpins)), n_samples,
+            int(seed) & (2**64 - 1),
             rows.ctypes.data if rows.size else None, weights.ctypes.data if weights.size else None,
             logz.ctypes.data if logz.size else None))
         out = [rows[int(offsets[s]) * n_samples:int(offsets[s + 1]) * n_samples].reshape(
             n_samples, int(lens[s])) for s in range(len(seqs))]
         return out, weights, logz
 
-    def mfe_batch(self, seqs, uses_contra_model, allows_short_hairpins):
+    def mfe_batch(self, seqs, uses_contra_model, allows_short_hairpins, constraints=None,
+                  max_bp_span=0):
         """Maximum-score structure of every sequence (rnamc_mfe_batch: MFE under Turner, the
         Viterbi parse under CONTRAfold) -> (list of dot-bracket str, scores f32[n_seqs] = the sum
-        of each structure's loop scores, dp_scores f32[n_seqs] = the max-plus sweep's value)."""
-        for s in seqs:
-            if len(s) == 0:
-                raise _lib.RnamcError(_lib.ERR_EMPTY_SEQ)
-        lens = np.array([len(s) for s in seqs], dtype=np.uint64)
-        offsets = np.zeros(len(seqs) + 1, dtype=np.uint64)
-        np.cumsum(lens, out=offsets[1:])
-        bases = np.concatenate([np.asarray(s, dtype=np.uint8) for s in seqs]) if seqs else \
-            np.zeros(0, np.uint8)
+        of each structure's loop scores, dp_scores f32[n_seqs] = the max-plus sweep's value).
+        constraints, max_bp_span: as bpp_batch."""
+        lens, offsets, bases = _pack(seqs)
+        cons = _constraint_bytes(constraints, lens)
         rows = np.empty(max(int(offsets[-1]), 1), dtype=np.uint8)
         scores = np.empty(len(seqs), dtype=np.float32)
         dp = np.empty(len(seqs), dtype=np.float32)
-        _lib.check(_lib.lib().rnamc_mfe_batch(
-            self._h, len(seqs), bases.ctypes.data, offsets.ctypes.data, int(bool(uses_contra_model)),
-            int(bool(allows_short_hairpins)), rows.ctypes.data,
+        _lib.check(_lib.lib().rnamc_mfe_batch_constrained(
+            self._h, len(seqs), bases.ctypes.data, offsets.ctypes.data, cons, _span(max_bp_span),
+            int(bool(uses_contra_model)), int(bool(allows_short_hairpins)), rows.ctypes.data,
             scores.ctypes.data if scores.size else None, dp.ctypes.data if dp.size else None))
         out = [bytes(rows[int(offsets[s]):int(offsets[s + 1])]).decode() for s in range(len(seqs))]
         return out, scores, dp
+
+    def log_partition_batch(self, seqs, uses_contra_model, allows_short_hairpins, constraints=None,
+                            max_bp_span=0):
+        """ln Z (ln Z_c under constraints, as bpp_batch) of every sequence: the reference-order
+        inside sweep alone (rnamc_log_partition_batch) -> f32[n_seqs], equal bit for bit to
+        bpp_batch's log partition in summation_mode 0."""
+        lens, offsets, bases = _pack(seqs)
+        cons = _constraint_bytes(constraints, lens)
+        logz = np.empty(max(len(seqs), 1), dtype=np.float32)
+        _lib.check(_lib.lib().rnamc_log_partition_batch(
+            self._h, len(seqs), bases.ctypes.data, offsets.ctypes.data, cons, _span(max_bp_span),
+            int(bool(uses_contra_model)), int(bool(allows_short_hairpins)), logz.ctypes.data))
+        return logz[:len(seqs)]
 
     def debug_fetch(self, seq_idx, which, n):
         out = np.empty((n, n), dtype=np.float32)
@@ -349,23 +398,19 @@ class Pool:
 
     __del__ = close
 
-    def bpp_batch(self, seqs, uses_contra_model, allows_short_hairpins):
-        for s in seqs:
-            if len(s) == 0:
-                raise _lib.RnamcError(_lib.ERR_EMPTY_SEQ)
-        lens = np.array([len(s) for s in seqs], dtype=np.uint64)
-        offsets = np.zeros(len(seqs) + 1, dtype=np.uint64)
-        np.cumsum(lens, out=offsets[1:])
-        bases = np.concatenate([np.asarray(s, dtype=np.uint8) for s in seqs]) if seqs else \
-            np.zeros(0, np.uint8)
+    def bpp_batch(self, seqs, uses_contra_model, allows_short_hairpins, constraints=None,
+                  max_bp_span=0):
+        """As Context.bpp_batch, sharded over the pool's contexts (rnamc_bpp_batch_multi)."""
+        lens, offsets, bases = _pack(seqs)
+        cons = _constraint_bytes(constraints, lens)
         out_offsets = np.zeros(len(seqs) + 1, dtype=np.uint64)
         np.cumsum(lens * (lens + 1) // 2, out=out_offsets[1:])
         bpp = np.empty(int(out_offsets[-1]), dtype=np.float32)
         logz = np.empty(len(seqs), dtype=np.float32)
-        _lib.check(_lib.lib().rnamc_bpp_batch_multi(
-            self._h, len(seqs), bases.ctypes.data, offsets.ctypes.data, int(bool(uses_contra_model)),
-            int(bool(allows_short_hairpins)), bpp.ctypes.data, out_offsets.ctypes.data,
-            logz.ctypes.data))
+        _lib.check(_lib.lib().rnamc_bpp_batch_multi_constrained(
+            self._h, len(seqs), bases.ctypes.data, offsets.ctypes.data, cons, _span(max_bp_span),
+            int(bool(uses_contra_model)), int(bool(allows_short_hairpins)), bpp.ctypes.data,
+            out_offsets.ctypes.data, logz.ctypes.data))
         mats = [BppMatrix(int(lens[s]), bpp[int(out_offsets[s]):int(out_offsets[s + 1])])
                 for s in range(len(seqs))]
         return mats, logz
@@ -463,13 +508,15 @@ def get_fold_sums_contra(seq, allows_short_hairpins, fold_score_sets):
     return _context_for(fold_score_sets).fold_sums(seq, True, allows_short_hairpins)
 
 
-def mccaskill_algo_batch(seqs, uses_contra_model, allows_short_hairpins, fold_score_sets):
+def mccaskill_algo_batch(seqs, uses_contra_model, allows_short_hairpins, fold_score_sets,
+                         constraints=None, max_bp_span=0):
     """Whole FASTA at once, over the process's devices (`default_devices`: every visible GPU unless
     RNAMC_DEVICES / LOCAL_RANK say otherwise) — what src/bin/mccaskill_algo.rs:58-93 does on all
-    cores with one pool task per record."""
+    cores with one pool task per record.  constraints (one string or None per sequence),
+    max_bp_span: hard constraints, as Context.bpp_batch."""
     with _ctx_lock:
         return _pool_for(fold_score_sets).bpp_batch(list(seqs), uses_contra_model,
-                                                    allows_short_hairpins)
+                                                    allows_short_hairpins, constraints, max_bp_span)
 
 
 def structure_score(seq, dot_bracket, uses_contra_model, allows_short_hairpins, fold_score_sets):
@@ -486,44 +533,134 @@ def structure_score(seq, dot_bracket, uses_contra_model, allows_short_hairpins, 
 
 
 def sample_structures_batch(seqs, n_samples, uses_contra_model, allows_short_hairpins,
-                            fold_score_sets, seed=0):
+                            fold_score_sets, seed=0, constraints=None, max_bp_span=0):
     """Boltzmann samples of every sequence on the process's shared context -> (per sequence a
     list of n_samples (dot_bracket, log_weight), log partition f32[n_seqs]).  Sample t of
-    sequence s depends on (tables, sequence, flags, seed, s, t) only."""
+    sequence s depends on (tables, sequence, constraint, flags, seed, s, t) only.  constraints
+    (one string or None per sequence), max_bp_span: hard constraints, as Context.bpp_batch."""
     seqs = [np.asarray(s, dtype=np.uint8) for s in seqs]
     for s in seqs:
         if s.shape[0] > MAX_SEQ_LEN:
             raise _lib.RnamcError(_lib.ERR_SEQ_TOO_LONG)
     with _ctx_lock:
         rows, weights, logz = _context_for(fold_score_sets).sample_batch(
-            seqs, n_samples, uses_contra_model, allows_short_hairpins, seed)
+            seqs, n_samples, uses_contra_model, allows_short_hairpins, seed, constraints, max_bp_span)
     out = [[(bytes(r).decode(), float(w)) for r, w in zip(m, ws)] for m, ws in zip(rows, weights)]
     return out, logz
 
 
 def sample_structures(seq, n_samples, uses_contra_model, allows_short_hairpins, fold_score_sets,
-                      seed=0):
+                      seed=0, constraints=None, max_bp_span=0):
     """n_samples structures of one sequence drawn with probability exp(score) / Z -> (list of
-    (dot_bracket, log_weight), ln Z)."""
+    (dot_bracket, log_weight), ln Z).  constraints: one constraint string (or None)."""
     out, logz = sample_structures_batch([seq], n_samples, uses_contra_model, allows_short_hairpins,
-                                        fold_score_sets, seed)
+                                        fold_score_sets, seed,
+                                        None if constraints is None else [constraints], max_bp_span)
     return out[0], float(logz[0])
 
 
-def mfe_fold_batch(seqs, uses_contra_model, allows_short_hairpins, fold_score_sets):
+def mfe_fold_batch(seqs, uses_contra_model, allows_short_hairpins, fold_score_sets,
+                   constraints=None, max_bp_span=0):
     """Maximum-score structure of every sequence on the process's shared context -> (list of
     (dot_bracket, score)); score is the f32 sum of the structure's loop scores (compare
-    structure_score).  Ties go to the first maximal candidate in the grammar's order."""
+    structure_score).  Ties go to the first maximal candidate in the grammar's order.
+    constraints (one string or None per sequence), max_bp_span: as Context.bpp_batch."""
     seqs = [np.asarray(s, dtype=np.uint8) for s in seqs]
     for s in seqs:
         if s.shape[0] > MAX_SEQ_LEN:
             raise _lib.RnamcError(_lib.ERR_SEQ_TOO_LONG)
     with _ctx_lock:
-        dbs, scores, _ = _context_for(fold_score_sets).mfe_batch(seqs, uses_contra_model,
-                                                                  allows_short_hairpins)
+        dbs, scores, _ = _context_for(fold_score_sets).mfe_batch(
+            seqs, uses_contra_model, allows_short_hairpins, constraints, max_bp_span)
     return [(db, float(w)) for db, w in zip(dbs, scores)]
 
 
-def mfe_fold(seq, uses_contra_model, allows_short_hairpins, fold_score_sets):
-    """Maximum-score (MFE / Viterbi) structure of one sequence -> (dot_bracket, score)."""
-    return mfe_fold_batch([seq], uses_contra_model, allows_short_hairpins, fold_score_sets)[0]
+def mfe_fold(seq, uses_contra_model, allows_short_hairpins, fold_score_sets, constraints=None,
+             max_bp_span=0):
+    """Maximum-score (MFE / Viterbi) structure of one sequence -> (dot_bracket, score).
+    constraints: one constraint string (or None)."""
+    return mfe_fold_batch([seq], uses_contra_model, allows_short_hairpins, fold_score_sets,
+                          None if constraints is None else [constraints], max_bp_span)[0]
+
+
+# ---- hard constraints (include/rnamc.h; DESIGN.md section 11) ----
+
+def log_partition_batch(seqs, uses_contra_model, allows_short_hairpins, fold_score_sets,
+                        constraints=None, max_bp_span=0):
+    """ln Z (ln Z_c under the constraints) of every sequence: the inside sweep alone, reference
+    order, on the process's shared context -> f32[n_seqs]."""
+    seqs = [np.asarray(s, dtype=np.uint8) for s in seqs]
+    for s in seqs:
+        if s.shape[0] > MAX_SEQ_LEN:
+            raise _lib.RnamcError(_lib.ERR_SEQ_TOO_LONG)
+    with _ctx_lock:
+        return _context_for(fold_score_sets).log_partition_batch(
+            seqs, uses_contra_model, allows_short_hairpins, constraints, max_bp_span)
+
+
+def constraint_probability(seq, constraint, uses_contra_model, allows_short_hairpins,
+                           fold_score_sets, max_bp_span=0):
+    """P(c) = Z_c / Z: the probability that a structure of the ensemble satisfies the constraint
+    string `constraint` (None: no string) and the span limit.  exp(ln Z_c - ln Z) from one
+    two-record batch of the inside-only entry (two calls when a span limit applies: it holds for
+    a whole call).  Values that f32 rounding puts above 1 are clipped."""
+    seq = np.asarray(seq, dtype=np.uint8)
+    n = int(seq.shape[0])
+    span = _span(max_bp_span)
+    if span == 0 or span >= n:
+        lz = log_partition_batch([seq, seq], uses_contra_model, allows_short_hairpins,
+                                 fold_score_sets, [None, constraint])
+        lz0, lzc = float(lz[0]), float(lz[1])
+    else:
+        lz0 = float(log_partition_batch([seq], uses_contra_model, allows_short_hairpins,
+                                        fold_score_sets)[0])
+        lzc = float(log_partition_batch([seq], uses_contra_model, allows_short_hairpins,
+                                        fold_score_sets, [constraint], span)[0])
+    return min(1.0, float(np.exp(np.float64(lzc) - np.float64(lz0))))
+
+
+def unpaired_probability(seq, regions, uses_contra_model, allows_short_hairpins, fold_score_sets):
+    """For each inclusive region (a, b) the probability that every base a..b is unpaired (its
+    accessibility) -> f64[len(regions)].  One batch: the unconstrained record and one record per
+    region with 'x' over it.  Values that f32 rounding puts above 1 are clipped."""
+    seq = np.asarray(seq, dtype=np.uint8)
+    n = int(seq.shape[0])
+    cons = [None]
+    for a, b in regions:
+        a, b = int(a), int(b)
+        if not 0 <= a <= b < n:
+            raise _lib.RnamcError(_lib.ERR_INVALID_ARG, f"region ({a}, {b}) outside 0 .. {n - 1}")
+        cons.append("." * a + "x" * (b - a + 1) + "." * (n - 1 - b))
+    lz = log_partition_batch([seq] * len(cons), uses_contra_model, allows_short_hairpins,
+                             fold_score_sets, cons).astype(np.float64)
+    return np.minimum(1.0, np.exp(lz[1:] - lz[0]))
+
+
+def check_constraint(constraint, n=None, max_bp_span=0):
+    """Raise RnamcError (ERR_INVALID_ARG, with the position) unless `constraint` is a valid
+    constraint string (of length n when n is given)."""
+    c = constraint.encode("ascii", errors="replace") if isinstance(constraint, str) else bytes(constraint)
+    if n is not None and len(c) != int(n):
+        raise _lib.RnamcError(_lib.ERR_INVALID_ARG, f"constraint has length {len(c)}, sequence {n}")
+    if b"\0" in c:
+        raise _lib.RnamcError(_lib.ERR_INVALID_ARG, f"constraint position {c.index(0)}: NUL byte")
+    if len(c) == 0:
+        raise _lib.RnamcError(_lib.ERR_EMPTY_SEQ)
+    _lib.check(_lib.lib().rnamc_constraint_check(c, len(c), _span(max_bp_span), None, None))
+
+
+def is_compatible(dot_bracket, constraint, max_bp_span=0):
+    """Does the structure `dot_bracket` satisfy the constraint string (None: none) and the span
+    limit?  (rnamc_constraint_check, host only; the model's own pair rules are not checked.)"""
+    db = dot_bracket.encode() if isinstance(dot_bracket, str) else bytes(dot_bracket)
+    if constraint is None:
+        constraint = b"." * len(db)
+    c = constraint.encode("ascii", errors="replace") if isinstance(constraint, str) else bytes(constraint)
+    if len(c) != len(db):
+        raise _lib.RnamcError(_lib.ERR_INVALID_ARG,
+                              f"constraint has length {len(c)}, structure {len(db)}")
+    if len(db) == 0:
+        raise _lib.RnamcError(_lib.ERR_EMPTY_SEQ)
+    out = C.c_int(0)
+    _lib.check(_lib.lib().rnamc_constraint_check(c, len(c), _span(max_bp_span), db, C.byref(out)))
+    return bool(out.value)

@@ -70,6 +70,27 @@ def read_fasta(path):
     return recs
 
 
+def read_fasta_raw(path):
+    """FASTA records as they are written: list of (id, str), lines of a record joined, nothing
+    decoded (constraint files: their characters are not bases)."""
+    recs, cur_id, cur = [], None, []
+    with open(path, "rb") as fh:
+        for line in fh:
+            line = line.strip()
+            if not line:
+                continue
+            if line.startswith(b">"):
+                if cur_id is not None:
+                    recs.append((cur_id, b"".join(cur).decode("ascii", errors="replace")))
+                cur_id = line[1:].split()[0].decode() if len(line) > 1 else ""
+                cur = []
+            else:
+                cur.append(line)
+    if cur_id is not None:
+        recs.append((cur_id, b"".join(cur).decode("ascii", errors="replace")))
+    return recs
+
+
 class FoldScoreSets:
     """`FoldScoreSets::new(init_val)` then `.transfer()` as every reference caller
     does (tests/tests.rs:21-22, src/bin/mccaskill_algo.rs:59-60)."""
