@@ -40,7 +40,7 @@ extern "C" {
  *    since, without a version change: rnamc_sample_batch, rnamc_structure_score,
  *    rnamc_mfe_batch, rnamc_bpp_batch_constrained, rnamc_bpp_batch_multi_constrained,
  *    rnamc_sample_batch_constrained, rnamc_mfe_batch_constrained, rnamc_log_partition_batch,
- *    rnamc_constraint_check */
+ *    rnamc_constraint_check, rnamc_centroid_fold_batch, rnamc_centroid_fold_batch_multi */
 #define RNAMC_ABI_VERSION 3u
 
 /* Compile-time limits.  In the reference these are constants of rna-ss-params
@@ -261,6 +261,9 @@ int rnamc_ctx_set_params(rnamc_ctx* ctx, const rnamc_params* params);
  * other's launch gaps: default 1; device-resident entry only), "tree_mid_mx" (the
  * mid-field products on the matrix cores, k_tree_mid_mx: exponentials per operand element, one
  * v_mfma_f32_32x32x2_f32 multiply-add per term; default 1, 0 = the VALU form k_tree_mid).
+ * rnamc_centroid_fold_batch: "centroid_chunk_bytes" (bytes of (max,+) matrices one chunk of
+ * (record, threshold) items may take; 0 — the default — = the workspace the context holds for the
+ * group; never more than that workspace, never less than one item; results do not depend on it).
  * Every knob is per context. */
 int rnamc_ctx_set(rnamc_ctx* ctx, const char* name, int64_t value);
 
@@ -546,6 +549,44 @@ int rnamc_centroid_fold_multi(rnamc_ctx* ctx, const float* bpp_packed, uint32_t 
                               const float* centroid_thresholds, uint32_t n_thresholds,
                               uint32_t* pairs_out, uint32_t max_pairs, uint32_t* n_pairs,
                               float* expect_accuracy);
+
+/* mccaskill_algo + centroid_fold for every record and every threshold (what the reference's
+ * centroid_fold binary does, src/bin/centroid_fold.rs:119-161); the bpp triangles never leave the
+ * device unless `bpp` is given.  The bpp come from the context's summation mode.  Per lock-step
+ * group the (max,+) fill of every (record, threshold) and its traceback run on the device off the
+ * group's triangles.
+ *   bases, offsets, constraints, max_bp_span, flags   as rnamc_bpp_batch_constrained
+ *   centroid_thresholds / n_thresholds               1 .. 65535 gammas, shared by all records
+ *   structs          per sequence s, n_thresholds rows of n_s bytes '(' ')' '.', at
+ *                    structs + n_thresholds * (offsets[s] - offsets[0]); row g at + g * n_s
+ *                    (the layout of rnamc_sample_batch with thresholds in place of samples)
+ *   n_pairs          n_seqs * n_thresholds u32, [s * n_thresholds + g]   (may be NULL)
+ *   expect_accuracy  n_seqs * n_thresholds f32, same indexing            (may be NULL)
+ *   log_partition    n_seqs f32                                          (may be NULL)
+ *   bpp, out_offsets as rnamc_bpp_batch; both NULL = do not return the triangles
+ * For each (s, g) the row, the count and expect_accuracy are exactly what rnamc_centroid_fold
+ * returns for the triangle this same call produced: the dot-bracket string of its pairs, their
+ * number, the same f32 bits.  The PUSH ORDER of the pairs is not part of this entry (the
+ * reference's binary only ever prints the string, src/bin/centroid_fold.rs:197-207).  Results do
+ * not depend on grouping, on the other records of the batch or on "centroid_chunk_bytes".
+ * RNAMC_ERR_INVALID_ARG for n_thresholds == 0, for bpp without out_offsets or the reverse, for a
+ * NULL ctx / pool; bad records and bad constraints fail before any device work. */
+int rnamc_centroid_fold_batch(rnamc_ctx* ctx, uint32_t n_seqs, const uint8_t* bases,
+                              const uint64_t* offsets, const char* constraints,
+                              uint32_t max_bp_span, int uses_contra_model,
+                              int allows_short_hairpins, const float* centroid_thresholds,
+                              uint32_t n_thresholds, uint8_t* structs, uint32_t* n_pairs,
+                              float* expect_accuracy, float* log_partition, float* bpp,
+                              const uint64_t* out_offsets);
+/* The same over the pool's devices: the shards of rnamc_bpp_batch_multi_constrained
+ * (rnamc_shard_plan), each through its own context, written straight into the caller's arrays. */
+int rnamc_centroid_fold_batch_multi(rnamc_pool* pool, uint32_t n_seqs, const uint8_t* bases,
+                                    const uint64_t* offsets, const char* constraints,
+                                    uint32_t max_bp_span, int uses_contra_model,
+                                    int allows_short_hairpins, const float* centroid_thresholds,
+                                    uint32_t n_thresholds, uint8_t* structs, uint32_t* n_pairs,
+                                    float* expect_accuracy, float* log_partition, float* bpp,
+                                    const uint64_t* out_offsets);
 
 /* ------------------------------------------------------------------------- */
 /* Durbin pair-HMM nucleotide match probabilities (SURVEY.md 8f-4;

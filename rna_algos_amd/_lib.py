@@ -32,7 +32,7 @@ SYMBOLS = [
     "rnamc_sweep_cost", "rnamc_sample_batch", "rnamc_structure_score", "rnamc_mfe_batch",
     "rnamc_bpp_batch_constrained", "rnamc_bpp_batch_multi_constrained",
     "rnamc_sample_batch_constrained", "rnamc_mfe_batch_constrained", "rnamc_log_partition_batch",
-    "rnamc_constraint_check",
+    "rnamc_constraint_check", "rnamc_centroid_fold_batch", "rnamc_centroid_fold_batch_multi",
 ]
 
 
@@ -166,6 +166,11 @@ def lib():
                                             C.c_int, vp]
     L.rnamc_constraint_check.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_char_p,
                                          C.POINTER(C.c_int)]
+    # (ctx or pool, n_seqs, bases, offsets, constraints, max_bp_span, contra, short hairpins, thresholds,
+    # n_thresholds, structs, n_pairs, expect_accuracy, log_partition, bpp, out_offsets)
+    L.rnamc_centroid_fold_batch.argtypes = [vp, C.c_uint32, vp, vp, C.c_char_p, C.c_uint32, C.c_int, C.c_int,
+                                            vp, C.c_uint32, vp, vp, vp, vp, vp, vp]
+    L.rnamc_centroid_fold_batch_multi.argtypes = L.rnamc_centroid_fold_batch.argtypes
     _lib = L
     return L
 

@@ -1,17 +1,20 @@
 """Mirror of the reference binary `centroid_fold` (src/bin/centroid_fold.rs:13-207):
 
     python -m rna_algos_amd.bin.centroid_fold -i FASTA -o DIR [-g GAMMA] [-c] [-t N]
+                                              [--constraints FILE] [--max-bp-span L]
 
-bpp matrices come from the GPU (one batch), the gamma-centroid folds from
-rnamc_centroid_fold; one file `centroid_threshold={gamma}.fa` per gamma (2^-7 .. 2^10
-when -g is absent) holding `>{index}\\n{dot-bracket}` records joined by `\\n`."""
+bpp matrices and the gamma-centroid folds of every record and threshold come from the GPU in one
+batch call (rnamc_centroid_fold_batch: the matrices never leave the device); one file
+`centroid_threshold={gamma}.fa` per gamma (2^-7 .. 2^10 when -g is absent) holding
+`>{index}\\n{dot-bracket}` records joined by `\\n`.  --constraints / --max-bp-span: hard constraints
+(bin/_constraints.py); without them the output is what it was."""
 import argparse
 import os
 import sys
 
-from ..centroid_fold import MAX_POW_2, MIN_POW_2, centroid_fold, centroid_fold_multi, get_fold_str
-from ..mccaskill_algo import Context, mccaskill_algo_batch
+from ..centroid_fold import MAX_POW_2, MIN_POW_2, centroid_fold, centroid_fold_batch, get_fold_str
 from ..utils import FoldScoreSets, NoTablesError, read_fasta, set_default_tables
+from . import _constraints
 from .mccaskill_algo import fmt_f32
 
 
@@ -25,7 +28,7 @@ def write_centroid_fold(mats, recs, centroid_threshold, path):
         fh.write("\n".join(parts))
 
 
-def main(argv=None):
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(prog="centroid_fold")
     ap.add_argument("-i", "--input_file_path", required=True)
     ap.add_argument("-o", "--output_dir_path", required=True)
@@ -36,7 +39,14 @@ def main(argv=None):
                     help="NOT the reference's parameters: seeded synthetic tables (testing only). "
                          "Without it $RNAMC_TABLES must name a table file dumped from the "
                          "rna-ss-params crate")
+    _constraints.add_args(ap)
     args = ap.parse_args(argv)
+    _constraints.check_span(ap, args)
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
     if args.synthetic_tables is not None:
         set_default_tables(FoldScoreSets.synthetic(args.synthetic_tables))
         print(f"warning: SYNTHETIC scoring tables (seed {args.synthetic_tables}): the output is "
@@ -48,26 +58,24 @@ def main(argv=None):
     except NoTablesError as e:
         print(f"error: {e}", file=sys.stderr)
         return 2
-    mats, _ = mccaskill_algo_batch([s for _, s in recs], args.uses_contra_model, False,
-                                   fold_score_sets)
-    os.makedirs(args.output_dir_path, exist_ok=True)
+    cons = None
+    if args.constraints is not None:
+        try:
+            cons = _constraints.load(args.constraints, recs)
+        except (_constraints.ConstraintFileError, OSError) as e:
+            print(f"error: {e}", file=sys.stderr)
+            return 2
     if args.centroid_threshold is not None:
         gammas = [args.centroid_threshold]
     else:
         gammas = [2.0 ** k for k in range(MIN_POW_2, MAX_POW_2 + 1)]
-    if len(gammas) == 1 and max(len(s) for _, s in recs) < 512:
-        # one threshold, short records: the host fold (a launch per anti-diagonal would cost more)
-        path = os.path.join(args.output_dir_path, f"centroid_threshold={fmt_f32(gammas[0])}.fa")
-        write_centroid_fold(mats, recs, gammas[0], path)
-        return 0
-    # every threshold of a record in one device sweep (bit-identical to the host fold)
-    ctx = Context(fold_score_sets)
-    folds = [centroid_fold_multi(ctx, m, len(seq), gammas) for (_, seq), m in zip(recs, mats)]
-    ctx.close()
+    # every record and threshold in one device call (strings bit-identical to the host fold's)
+    folds, _ = centroid_fold_batch([s for _, s in recs], gammas, args.uses_contra_model, False,
+                                   fold_score_sets, cons, args.max_bp_span)
+    os.makedirs(args.output_dir_path, exist_ok=True)
     for x, g in enumerate(gammas):
         path = os.path.join(args.output_dir_path, f"centroid_threshold={fmt_f32(g)}.fa")
-        parts = [f">{rna_id}\n" + get_fold_str(folds[rna_id][x], len(seq))
-                 for rna_id, (_, seq) in enumerate(recs)]
+        parts = [f">{rna_id}\n" + folds[rna_id][x][0] for rna_id in range(len(recs))]
         with open(path, "w") as fh:
             fh.write("\n".join(parts))
     return 0

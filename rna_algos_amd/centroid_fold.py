@@ -45,6 +45,22 @@ def centroid_fold_multi(ctx, basepair_probs, seq_len, centroid_thresholds):
             for x in range(len(g))]
 
 
+def centroid_fold_batch(seqs, centroid_thresholds, uses_contra_model, allows_short_hairpins,
+                        fold_score_sets, constraints=None, max_bp_span=0, return_bpp=False):
+    """What the reference's centroid_fold binary computes (src/bin/centroid_fold.rs:119-161), whole
+    FASTA at once over the process's devices: mccaskill_algo and the centroid fold of every record
+    for every threshold on the GPU (rnamc_centroid_fold_batch_multi); the bpp matrices stay on the
+    device unless return_bpp is set.  Returns (folds, log_z) or (folds, log_z, mats) with
+    folds[s][g] = (dot_bracket, expect_accuracy); each fold is what centroid_fold gives for the
+    matrix of the same call (string of its pairs and accuracy bit for bit).  constraints (one
+    string or None per sequence), max_bp_span: hard constraints, as mccaskill_algo_batch."""
+    from . import mccaskill_algo as M
+    with M._ctx_lock:
+        return M._pool_for(fold_score_sets).centroid_fold_batch(
+            list(seqs), centroid_thresholds, uses_contra_model, allows_short_hairpins, constraints,
+            max_bp_span, return_bpp)
+
+
 def get_fold_str(fold, seq_len):
     """src/bin/centroid_fold.rs:197-207"""
     s = [UNPAIR] * seq_len

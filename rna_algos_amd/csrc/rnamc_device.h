@@ -115,6 +115,40 @@ struct CentroidBatch {
 };
 void launch_centroid(const CentroidBatch& a, uint32_t d, uint32_t n_gammas, hipStream_t st);
 
+// gamma-centroid folds of a batch (rnamc_centroid_batch.hip).  An item is one (sequence, threshold)
+// pair; its (max,+) matrix is ONE packed diagonal-major triangle laid out like the bpp triangle
+// (cell (i, j) at d*n - d(d-1)/2 + i, d = j - i; the main diagonal holds zeros), so the cells of a
+// diagonal on consecutive rows read consecutive floats for both factors of every bifurcation.
+struct CentroidItem {
+  uint64_t m_off;    // float offset of the item's triangle in `m` (mpad floats, see centroid_item_floats)
+  uint64_t bpp_off;  // float offset of its sequence's bpp triangle in `bpp`
+  uint64_t row_off;  // byte offset of its n bytes '(' ')' '.' in `rows`
+  uint32_t n;
+  float gamma;
+};
+struct CentroidChunk {
+  const CentroidItem* items;  // device; longest sequence first (items with n > d are a prefix)
+  const float* bpp;           // the group's packed triangles, absent pairs negative
+  float* m;
+  uint8_t* rows;
+  uint32_t* n_pairs;          // [item]; 0xffffffff = the traceback's stack overflowed (nothing written)
+  float* expect_accuracy;     // [item] M(0, n-1)
+  uint64_t* stack;            // n_waves slices of stack_cap pending intervals
+  uint32_t n_items, stack_cap;
+};
+inline uint64_t centroid_item_floats(uint32_t n) {
+  return ((static_cast<uint64_t>(n) * (n + 1ull) / 2ull) + 63ull) & ~63ull;
+}
+// out[x] = the largest entry of sequence x's bpp triangle (seqs[x].bpp_off, seqs[x].n; -1 when no pair is present)
+void launch_centroid_pmax(const CentroidItem* seqs, const float* bpp, float* out, uint32_t nseq, hipStream_t st);
+// zeros on the main diagonal of every item's triangle
+void launch_centroid_batch_init(const CentroidChunk& a, uint32_t max_n, hipStream_t st);
+// diagonal d (1 <= d < max_n) of the first n_active items (those with n > d; at most 65535)
+void launch_centroid_batch(const CentroidChunk& a, uint32_t d, uint32_t n_active, uint32_t max_n,
+                           hipStream_t st);
+// traceback of every item: one wave per item; n_waves a multiple of 4 (256-thread blocks)
+void launch_centroid_trace(const CentroidChunk& a, uint32_t n_waves, hipStream_t st);
+
 // ---- tree-order summation mode (rnamc_tree.hip) ----
 // Dense n x n matrices with row stride ld (>= n + 32, a multiple of 32 floats), msz floats
 // each; "row" = [i * ld + j], "col" = [j * ld + i].  The outside sweep reuses four slots.

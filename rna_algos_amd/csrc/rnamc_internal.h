@@ -22,6 +22,19 @@ void hp_init_table(const rnamc_turner_scores& t, uint32_t len, float* out);
 // byte outside the set or an unbalanced bracket, with its position in *bad_pos and the reason in *why.
 int compile_constraint(const char* str, uint32_t n, int32_t* words, uint32_t* bad_pos, const char** why);
 
+// rnamc_centroid_fold_batch behind its two entries (rnamc_api.cpp): the arguments of the entry after
+// centroid_fold_batch_check, plus where sequence s writes — its rows at structs + struct_offs[s], its
+// per-threshold results at index res_idx[s] * n_thresholds, its log partition at res_idx[s]
+int centroid_fold_batch_check(uint32_t n_seqs, const uint8_t* bases, const uint64_t* offsets,
+                              const float* gammas, uint32_t ng, const uint8_t* structs, const float* bpp,
+                              const uint64_t* out_offsets);
+int centroid_fold_batch_core(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* bases, const uint64_t* offsets,
+                             const char* constraints, uint32_t max_bp_span, int uses_contra_model,
+                             int allows_short_hairpins, const float* gammas, uint32_t ng, uint8_t* structs,
+                             const uint64_t* struct_offs, const uint32_t* res_idx, uint32_t* n_pairs,
+                             float* expect_accuracy, float* log_partition, float* bpp,
+                             const uint64_t* out_offsets);
+
 // DP matrices of one sequence inside the workspace.  Every matrix is a packed
 // upper triangle of n(n+1)/2 f32 (padded to a multiple of 64 floats):
 //  - "diag-major": cell (i,j) at  d*n - d(d-1)/2 + i  with d = j-i.  A lane that

@@ -261,4 +261,98 @@ int rnamc_bpp_batch_multi_constrained(rnamc_pool* p, uint32_t n_seqs, const uint
   return RNAMC_OK;
 }
 
+// rnamc_centroid_fold_batch over the pool: the shards of rnamc_bpp_batch_multi_constrained, each through
+// its own context, rows, counts, accuracies, log partitions and triangles written straight into the
+// caller's arrays.
+int rnamc_centroid_fold_batch_multi(rnamc_pool* p, uint32_t n_seqs, const uint8_t* bases,
+                                    const uint64_t* offsets, const char* constraints, uint32_t max_bp_span,
+                                    int uses_contra_model, int allows_short_hairpins,
+                                    const float* centroid_thresholds, uint32_t n_thresholds, uint8_t* structs,
+                                    uint32_t* n_pairs, float* expect_accuracy, float* log_partition, float* bpp,
+                                    const uint64_t* out_offsets) {
+  if (!p) return RNAMC_ERR_INVALID_ARG;
+  if (int rc = rnamc::centroid_fold_batch_check(n_seqs, bases, offsets, centroid_thresholds, n_thresholds,
+                                                structs, bpp, out_offsets))
+    return rc;
+  if (p->ctxs.empty()) return RNAMC_ERR_INVALID_ARG;
+  if (n_seqs == 0) return RNAMC_OK;
+  if (constraints) {  // the whole batch before any device sees a part of it (the span limit needs no check)
+    std::vector<int32_t> words;
+    for (uint32_t s = 0; s < n_seqs; s++) {
+      const uint32_t n = static_cast<uint32_t>(offsets[s + 1] - offsets[s]);
+      uint32_t bad = 0;
+      const char* why = "";
+      int rc = RNAMC_OK;
+      try {  // nothing may throw across the C boundary
+        words.resize(2ull * n);
+        rc = rnamc::compile_constraint(constraints + (offsets[s] - offsets[0]), n, words.data(), &bad, &why);
+      } catch (const std::exception&) {
+        rnamc::set_last_error("constraints: no host memory");
+        return RNAMC_ERR_OOM;
+      }
+      if (rc) {
+        rnamc::set_last_error("constraint of record " + std::to_string(s) + ", position " +
+                              std::to_string(bad) + ": " + why);
+        return rc;
+      }
+    }
+  }
+  std::lock_guard<std::mutex> lock(p->mu);
+  const uint32_t n_shards = static_cast<uint32_t>(std::min<size_t>(p->ctxs.size(), n_seqs));
+  std::vector<uint32_t> shard_of(n_seqs), order;
+  plan(n_seqs, offsets, n_shards, shard_of.data(), &order);
+  struct Shard {
+    std::vector<uint32_t> members;  // batch indices, longest first
+    std::vector<uint8_t> bases;
+    std::vector<char> cons;
+    std::vector<uint64_t> offsets, out_offsets, struct_offs;
+    int status = RNAMC_OK;
+    std::string error;
+  };
+  std::vector<Shard> shards(n_shards);
+  for (uint32_t x = 0; x < n_seqs; x++) shards[shard_of[order[x]]].members.push_back(order[x]);
+  for (Shard& sh : shards) {
+    uint64_t total = 0;
+    for (uint32_t s : sh.members) total += offsets[s + 1] - offsets[s];
+    sh.bases.resize(total);
+    if (constraints) sh.cons.resize(total);
+    sh.offsets.assign(1, 0);
+    for (uint32_t s : sh.members) {
+      const uint64_t n = offsets[s + 1] - offsets[s];
+      std::memcpy(sh.bases.data() + sh.offsets.back(), bases + offsets[s], n);
+      if (constraints) std::memcpy(sh.cons.data() + sh.offsets.back(), constraints + (offsets[s] - offsets[0]), n);
+      sh.offsets.push_back(sh.offsets.back() + n);
+      sh.struct_offs.push_back(static_cast<uint64_t>(n_thresholds) * (offsets[s] - offsets[0]));
+      if (bpp) sh.out_offsets.push_back(out_offsets[s]);
+    }
+  }
+  auto work = [&](uint32_t k) {
+    Shard& sh = shards[k];
+    if (sh.members.empty()) return;
+    // (the members themselves are the result indices: the shard writes the caller's arrays)
+    sh.status = rnamc::centroid_fold_batch_core(
+        p->ctxs[k], static_cast<uint32_t>(sh.members.size()), sh.bases.data(), sh.offsets.data(),
+        constraints ? sh.cons.data() : nullptr, max_bp_span, uses_contra_model, allows_short_hairpins,
+        centroid_thresholds, n_thresholds, structs, sh.struct_offs.data(), sh.members.data(), n_pairs,
+        expect_accuracy, log_partition, bpp, bpp ? sh.out_offsets.data() : nullptr);
+    if (sh.status) sh.error = rnamc_last_error();  // (thread-local: carry it to the caller's thread)
+  };
+  std::vector<std::thread> pool;
+  for (uint32_t k = 1; k < n_shards; k++) {
+    try {
+      pool.emplace_back(work, k);
+    } catch (...) {  // no thread: this shard runs on the caller's thread below
+      work(k);
+    }
+  }
+  work(0);
+  for (std::thread& t : pool) t.join();
+  for (const Shard& sh : shards)
+    if (sh.status) {
+      rnamc::set_last_error(sh.error);
+      return sh.status;
+    }
+  return RNAMC_OK;
+}
+
 }  // extern "C"

@@ -74,6 +74,41 @@ def _pack(seqs):
     return lens, offsets, bases
 
 
+def _centroid_fold_batch(entry, handle, seqs, centroid_thresholds, uses_contra_model,
+                         allows_short_hairpins, constraints, max_bp_span, return_bpp):
+    """rnamc_centroid_fold_batch / _multi on `handle` -> (folds, log partition f32[n_seqs]) or
+    (folds, log partition, list of BppMatrix): folds[s][g] = (dot_bracket, expect_accuracy f32)."""
+    lens, offsets, bases = _pack(seqs)
+    cons = _constraint_bytes(constraints, lens)
+    gammas = np.ascontiguousarray(centroid_thresholds, dtype=np.float32).reshape(-1)
+    ng = len(gammas)
+    rows = np.empty(max(int(offsets[-1]) * ng, 1), dtype=np.uint8)
+    npairs = np.zeros(max(len(seqs) * ng, 1), dtype=np.uint32)
+    acc = np.zeros(max(len(seqs) * ng, 1), dtype=np.float32)
+    logz = np.empty(max(len(seqs), 1), dtype=np.float32)
+    bpp = out_offsets = None
+    if return_bpp:
+        out_offsets = np.zeros(len(seqs) + 1, dtype=np.uint64)
+        np.cumsum(lens * (lens + 1) // 2, out=out_offsets[1:])
+        bpp = np.empty(max(int(out_offsets[-1]), 1), dtype=np.float32)
+    _lib.check(entry(
+        handle, len(seqs), bases.ctypes.data, offsets.ctypes.data, cons, _span(max_bp_span),
+        int(bool(uses_contra_model)), int(bool(allows_short_hairpins)), gammas.ctypes.data, ng,
+        rows.ctypes.data, npairs.ctypes.data, acc.ctypes.data, logz.ctypes.data,
+        bpp.ctypes.data if return_bpp else None, out_offsets.ctypes.data if return_bpp else None))
+    folds = []
+    for s in range(len(seqs)):
+        n, base = int(lens[s]), int(offsets[s]) * ng
+        block = bytes(rows[base:base + n * ng]).decode()
+        folds.append([(block[g * n:(g + 1) * n], acc[s * ng + g]) for g in range(ng)])
+    logz = logz[:len(seqs)]
+    if not return_bpp:
+        return folds, logz
+    mats = [BppMatrix(int(lens[s]), bpp[int(out_offsets[s]):int(out_offsets[s + 1])])
+            for s in range(len(seqs))]
+    return folds, logz, mats
+
+
 class BppMatrix:
     """One sequence's result: packed triangle of f32, absent pairs hold -1.0.
     `sparse()` gives the reference's SparseProbMat<T> as a dict {(i, j): p}."""
@@ -354,6 +389,16 @@ class Context:
             int(bool(uses_contra_model)), int(bool(allows_short_hairpins)), logz.ctypes.data))
         return logz[:len(seqs)]
 
+    def centroid_fold_batch(self, seqs, centroid_thresholds, uses_contra_model, allows_short_hairpins,
+                            constraints=None, max_bp_span=0, return_bpp=False):
+        """mccaskill_algo + centroid_fold of every sequence for every threshold on the device
+        (rnamc_centroid_fold_batch) -> (folds, log partition f32[n_seqs]) with folds[s][g] =
+        (dot_bracket, expect_accuracy), plus the list of BppMatrix when return_bpp is set.
+        constraints, max_bp_span: as bpp_batch."""
+        return _centroid_fold_batch(_lib.lib().rnamc_centroid_fold_batch, self._h, list(seqs),
+                                    centroid_thresholds, uses_contra_model, allows_short_hairpins,
+                                    constraints, max_bp_span, return_bpp)
+
     def debug_fetch(self, seq_idx, which, n):
         out = np.empty((n, n), dtype=np.float32)
         _lib.check(_lib.lib().rnamc_debug_fetch(self._h, seq_idx, which, out.ctypes.data))
@@ -414,6 +459,14 @@ class Pool:
         mats = [BppMatrix(int(lens[s]), bpp[int(out_offsets[s]):int(out_offsets[s + 1])])
                 for s in range(len(seqs))]
         return mats, logz
+
+    def centroid_fold_batch(self, seqs, centroid_thresholds, uses_contra_model, allows_short_hairpins,
+                            constraints=None, max_bp_span=0, return_bpp=False):
+        """As Context.centroid_fold_batch, sharded over the pool's contexts
+        (rnamc_centroid_fold_batch_multi)."""
+        return _centroid_fold_batch(_lib.lib().rnamc_centroid_fold_batch_multi, self._h, list(seqs),
+                                    centroid_thresholds, uses_contra_model, allows_short_hairpins,
+                                    constraints, max_bp_span, return_bpp)
 
 
 def shard_plan(lengths, n_shards):
