@@ -193,7 +193,7 @@ enum TreeMat : int {
   // probs_multibranch (outside); the statics (T_HP .. T_NEAR8): cell (i, j) at [(j - i) * ld + i] too
 };
 // Length-dependent part of a generic 2-loop score per probe slot (rnamc_tree.hip, probe_slot),
-// derived from rnamc_params on the host (rnamc_api.cpp, build_tree_tabs).  Model index 0 Turner,
+// derived from rnamc_params on the host (rnamc_sweep_tree.cpp, build_tree_tabs).  Model index 0 Turner,
 // 1 CONTRAfold.
 struct TreeTabs {
   float len[2][512];

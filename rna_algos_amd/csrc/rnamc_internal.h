@@ -22,7 +22,7 @@ void hp_init_table(const rnamc_turner_scores& t, uint32_t len, float* out);
 // byte outside the set or an unbalanced bracket, with its position in *bad_pos and the reason in *why.
 int compile_constraint(const char* str, uint32_t n, int32_t* words, uint32_t* bad_pos, const char** why);
 
-// rnamc_centroid_fold_batch behind its two entries (rnamc_api.cpp): the arguments of the entry after
+// rnamc_centroid_fold_batch behind its two entries (rnamc_entries_centroid.cpp): the arguments of the entry after
 // centroid_fold_batch_check, plus where sequence s writes — its rows at structs + struct_offs[s], its
 // per-threshold results at index res_idx[s] * n_thresholds, its log partition at res_idx[s]
 int centroid_fold_batch_check(uint32_t n_seqs, const uint8_t* bases, const uint64_t* offsets,

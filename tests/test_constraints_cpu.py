@@ -120,6 +120,71 @@ def test_entry_rejects_bad_records_before_device(built):
             assert want in L.rnamc_last_error().decode(), (name, L.rnamc_last_error())
 
 
+def test_entry_record_errors_and_check_order(built):
+    """the five host-buffer entries share one record check and keep their own order of checks, all before
+    the context is used (a dummy handle, as above): decreasing offsets, an empty record, a record above
+    the length limit (decided from the offsets alone: its bases are all invalid here) and a base of 4;
+    rnamc_mfe_batch_constrained tests a null `structs` before the constraints,
+    rnamc_sample_batch_constrained its n_samples == 0 and `structs` after them"""
+    L = _lib.lib()
+    dummy = np.zeros(64, np.uint8)
+    gam = np.array([0.5, 2.0], np.float32)
+    rows = np.zeros(2 * 65536, np.uint8)
+    vals = np.zeros(8, np.float32)
+    bpp = np.zeros(64, np.float32)
+    out_off = np.array([0, 10, 31], np.uint64)
+
+    def entries(n_seqs, bases, offsets, cons=None, structs=rows.ctypes.data, n_samples=3):
+        b, o = bases.ctypes.data, offsets.ctypes.data
+        return {
+            "bpp": lambda: L.rnamc_bpp_batch_constrained(dummy.ctypes.data, n_seqs, b, o, cons, 0, 0, 0,
+                                                         bpp.ctypes.data, out_off.ctypes.data, None),
+            "sample": lambda: L.rnamc_sample_batch_constrained(dummy.ctypes.data, n_seqs, b, o, cons, 0, 0, 0,
+                                                               n_samples, 1, structs, None, None),
+            "mfe": lambda: L.rnamc_mfe_batch_constrained(dummy.ctypes.data, n_seqs, b, o, cons, 0, 0, 0, structs,
+                                                         None, None),
+            "logz": lambda: L.rnamc_log_partition_batch(dummy.ctypes.data, n_seqs, b, o, cons, 0, 0, 0,
+                                                        vals.ctypes.data),
+            "centroid": lambda: L.rnamc_centroid_fold_batch(dummy.ctypes.data, n_seqs, b, o, cons, 0, 0, 0,
+                                                            gam.ctypes.data, 2, structs, None, None, None, None,
+                                                            None),
+        }
+
+    good = np.array([0, 1, 2, 3, 0, 1, 2, 3, 0, 1], np.uint8)
+    base4 = good.copy()
+    base4[7] = 4
+    cases = [
+        ("decreasing offsets", 2, good, np.array([0, 6, 4], np.uint64), _lib.ERR_INVALID_ARG),
+        ("empty record", 2, good, np.array([0, 4, 4], np.uint64), _lib.ERR_EMPTY_SEQ),
+        ("record of 65536", 1, np.full(65536, 4, np.uint8), np.array([0, 65536], np.uint64),
+         _lib.ERR_SEQ_TOO_LONG),
+        ("base of 4", 2, base4, np.array([0, 4, 10], np.uint64), _lib.ERR_INVALID_BASE),
+    ]
+    for what, n_seqs, bases, offsets, want in cases:
+        for name, call in entries(n_seqs, bases, offsets).items():
+            assert call() == want, (what, name)
+    # a record error comes before a constraint error
+    for name, call in entries(2, base4, np.array([0, 4, 10], np.uint64), cons=b"....(.(...").items():
+        assert call() == _lib.ERR_INVALID_BASE, name
+
+    offsets = np.array([0, 4, 10], np.uint64)
+    bad_cons = b"....(.(..."
+
+    def fresh_message():  # a message of another kind first, so that the one read afterwards is the call's own
+        assert L.rnamc_constraint_check(b"|", 1, 0, None, None) == _lib.ERR_INVALID_ARG
+        assert "record" not in L.rnamc_last_error().decode()
+
+    fresh_message()
+    assert entries(2, good, offsets, cons=bad_cons, structs=None)["mfe"]() == _lib.ERR_INVALID_ARG
+    assert "record" not in L.rnamc_last_error().decode()  # (the null `structs`, not the constraint)
+    fresh_message()
+    assert entries(2, good, offsets, cons=bad_cons, n_samples=0)["sample"]() == _lib.ERR_INVALID_ARG
+    assert "record 1, position 2" in L.rnamc_last_error().decode()
+    fresh_message()
+    assert entries(2, good, offsets, cons=bad_cons, structs=None)["sample"]() == _lib.ERR_INVALID_ARG
+    assert "record 1, position 2" in L.rnamc_last_error().decode()
+
+
 def test_python_length_mismatch(built):
     """a string whose length differs from its sequence fails before any device use"""
     seqs = [np.array([0, 1, 2, 3, 0], np.uint8)]
