@@ -61,6 +61,7 @@ extern "C" {
   fn rnamc_pool_set(pool: *mut RnamcPool, name: *const c_char, value: i64) -> c_int;
   fn rnamc_bpp_len(n: u32) -> u64;
   fn rnamc_bpp_batch_multi(pool: *mut RnamcPool, n_seqs: u32, bases: *const u8, offsets: *const u64, uses_contra_model: c_int, allows_short_hairpins: c_int, bpp: *mut f32, out_offsets: *const u64, log_partition: *mut f32) -> c_int;
+  fn rnamc_bpp_batch_sparse_multi(pool: *mut RnamcPool, n_seqs: u32, bases: *const u8, offsets: *const u64, constraints: *const c_char, max_bp_span: u32, uses_contra_model: c_int, allows_short_hairpins: c_int, min_prob: f32, pair_start: *mut u64, pair_count: *mut u64, pair_i: *mut u32, pair_j: *mut u32, pair_prob: *mut f32, pairs_cap: u64, pairs_total: *mut u64, paired_prob: *mut f32, log_partition: *mut f32) -> c_int;
   fn rnamc_fold_scores(ctx: *mut RnamcCtx, bases: *const u8, n: u32, uses_contra_model: c_int, allows_short_hairpins: c_int, hairpin_scores: *mut f32, multibranch_close_scores: *mut f32, accessible_scores: *mut f32, twoloop_scores: *mut TwoloopScore, twoloop_cap: u64, twoloop_count: *mut u64) -> c_int;
   fn rnamc_fold_sums(ctx: *mut RnamcCtx, bases: *const u8, n: u32, uses_contra_model: c_int, allows_short_hairpins: c_int, sums_external: *mut f32, sums_rightmost_basepairs_external: *mut f32, sums_rightmost_basepairs_multibranch: *mut f32, sums_close: *mut f32, sums_accessible: *mut f32, sums_multibranch: *mut f32, sums_1ormore_basepairs: *mut f32) -> c_int;
   fn rnamc_sample_batch(ctx: *mut RnamcCtx, n_seqs: u32, bases: *const u8, offsets: *const u64, uses_contra_model: c_int, allows_short_hairpins: c_int, n_samples: u32, seed: u64, structs: *mut u8, log_weights: *mut f32, log_partition: *mut f32) -> c_int;
@@ -334,6 +335,78 @@ where
     .iter()
     .enumerate()
     .map(|(s, seq)| unpack_probs::<T>(&packed[out_offsets[s] as usize..out_offsets[s + 1] as usize], seq.len()))
+    .collect()
+}
+
+// mccaskill_algo_batch keeping only the pairs with p >= min_prob (finite, >= 0; 0 keeps every
+// key), compacted on the device (rnamc_bpp_batch_sparse_multi): the dense triangles never reach
+// the host.  The lists are sized at a few entries per nucleotide (capped at the cells that can
+// pair); a call that reports more is repeated once with the exact total.
+pub fn mccaskill_algo_batch_sparse<T>(
+  seqs: &[SeqSlice],
+  uses_contra_model: bool,
+  allows_short_hairpins: bool,
+  fold_score_sets: &FoldScoreSets,
+  min_prob: f32,
+) -> Vec<SparseProbMat<T>>
+where
+  T: HashIndex,
+{
+  let mut bases = Vec::<u8>::new();
+  let mut offsets = vec![0u64];
+  let mut most = 0u64;
+  for seq in seqs {
+    bases.extend(seq.iter().map(|&x| x as u8));
+    offsets.push(bases.len() as u64);
+    most += unsafe { rnamc_bpp_len(seq.len() as u32) } - seq.len() as u64;
+  }
+  let (mut pair_start, mut pair_count) = (vec![0u64; seqs.len().max(1)], vec![0u64; seqs.len().max(1)]);
+  let mut cap = (4 * bases.len() as u64).min(most).max(1);
+  let (mut pair_i, mut pair_j, mut pair_prob) = (Vec::<u32>::new(), Vec::<u32>::new(), Vec::<f32>::new());
+  with_pool(fold_score_sets, |pool| {
+    for attempt in 0..2 {
+      pair_i.resize(cap as usize, 0);
+      pair_j.resize(cap as usize, 0);
+      pair_prob.resize(cap as usize, 0.);
+      let mut total = 0u64;
+      let status = unsafe {
+        rnamc_bpp_batch_sparse_multi(
+          pool,
+          seqs.len() as u32,
+          bases.as_ptr(),
+          offsets.as_ptr(),
+          std::ptr::null(),
+          0,
+          uses_contra_model as c_int,
+          allows_short_hairpins as c_int,
+          min_prob,
+          pair_start.as_mut_ptr(),
+          pair_count.as_mut_ptr(),
+          pair_i.as_mut_ptr(),
+          pair_j.as_mut_ptr(),
+          pair_prob.as_mut_ptr(),
+          cap,
+          &mut total,
+          std::ptr::null_mut(),
+          std::ptr::null_mut(),
+        )
+      };
+      if status != 0 && attempt == 0 && total > cap {
+        cap = total;
+        continue;
+      }
+      check(status, "rnamc_bpp_batch_sparse_multi");
+      break;
+    }
+  });
+  (0..seqs.len())
+    .map(|s| {
+      let mut basepair_probs = SparseProbMat::<T>::default();
+      for x in pair_start[s] as usize..(pair_start[s] + pair_count[s]) as usize {
+        basepair_probs.insert((T::from_usize(pair_i[x] as usize).unwrap(), T::from_usize(pair_j[x] as usize).unwrap()), pair_prob[x]);
+      }
+      basepair_probs
+    })
     .collect()
 }
 

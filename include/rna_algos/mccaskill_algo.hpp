@@ -241,6 +241,48 @@ std::vector<SparseProbMat<T>> mccaskill_algo_batch(const Context& ctx, const std
   return out;
 }
 
+// mccaskill_algo_batch keeping only the pairs with p >= min_prob (finite, >= 0; 0 keeps every key),
+// compacted on the device (rnamc_bpp_batch_sparse): the dense triangles never reach the host.  The
+// lists are sized at a few entries per nucleotide (capped at the cells that can pair); a call that
+// reports more is repeated once with the exact total.
+template <class T>
+std::vector<SparseProbMat<T>> mccaskill_algo_batch_sparse(const Context& ctx, const std::vector<Seq>& seqs,
+                                                          bool uses_contra_model, bool allows_short_hairpins,
+                                                          float min_prob) {
+  std::vector<uint64_t> off(seqs.size() + 1, 0);
+  uint64_t most = 0;
+  for (size_t s = 0; s < seqs.size(); s++) {
+    off[s + 1] = off[s] + seqs[s].size();
+    most += rnamc_bpp_len(static_cast<uint32_t>(seqs[s].size())) - seqs[s].size();
+  }
+  std::vector<Base> bases(off.back());
+  for (size_t s = 0; s < seqs.size(); s++) std::copy(seqs[s].begin(), seqs[s].end(), bases.begin() + off[s]);
+  std::vector<uint64_t> start(seqs.size() + 1), count(seqs.size() + 1);
+  std::vector<uint32_t> pi, pj;
+  std::vector<float> pp;
+  uint64_t cap = std::max<uint64_t>(std::min<uint64_t>(4 * off.back(), most), 1), total = 0;
+  for (int attempt = 0; attempt < 2; attempt++) {
+    pi.resize(cap);
+    pj.resize(cap);
+    pp.resize(cap);
+    const int st = rnamc_bpp_batch_sparse(ctx.get(), static_cast<uint32_t>(seqs.size()), bases.data(), off.data(),
+                                          nullptr, 0, uses_contra_model, allows_short_hairpins, min_prob,
+                                          start.data(), count.data(), pi.data(), pj.data(), pp.data(), cap, &total,
+                                          nullptr, nullptr);
+    if (st != RNAMC_OK && attempt == 0 && total > cap) {
+      cap = total;
+      continue;
+    }
+    check(st);
+    break;
+  }
+  std::vector<SparseProbMat<T>> out(seqs.size());
+  for (size_t s = 0; s < seqs.size(); s++)
+    for (uint64_t x = start[s]; x < start[s] + count[s]; x++)
+      out[s].emplace(PosPair<T>(static_cast<T>(pi[x]), static_cast<T>(pj[x])), pp[x]);
+  return out;
+}
+
 // Boltzmann sampling (rnamc_sample_batch; no counterpart in the reference): n_samples structures
 // per sequence, each drawn with probability exp(log_weight) / exp(log_partition).  Sample t of
 // sequence s is a pure function of (tables, sequence, flags, seed, s, t).

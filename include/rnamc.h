@@ -627,6 +627,53 @@ int rnamc_durbin_batch(rnamc_ctx* ctx, const rnamc_align_scores* scores, uint32_
                        const uint32_t* pair_a, const uint32_t* pair_b, float* match_probs,
                        const uint64_t* out_offsets);
 
+/* ------------------------------------------------------------------------- */
+/* Thresholded sparse pair probabilities (the reference's SparseProbMat, src/utils.rs), compacted
+ * on the device: the triangles never reach the host.
+ *   bases, offsets, constraints, max_bp_span, flags   as rnamc_bpp_batch_constrained
+ *   min_prob      finite and >= 0.  A pair (i, j), i < j, of record s is LISTED when it is present in
+ *                 the record's triangle (p > -0.5) and p >= min_prob (an f32 comparison).  0 lists
+ *                 exactly the keys of the reference's SparseProbMat; values above 1 are legal.
+ *   pair_i, pair_j, pair_prob   three parallel arrays of pairs_cap entries: all given, or all NULL
+ *   pair_start, pair_count      n_seqs u64 each: record s's pairs are entries
+ *                 [pair_start[s], pair_start[s] + pair_count[s]) of the three arrays, in packed-
+ *                 triangle order (span ascending, then i ascending).  Lists of different records
+ *                 never overlap; where a record's list sits is unspecified and may differ between
+ *                 calls (it follows group and shard order).
+ *   pairs_total   Sum of pair_count (never NULL)
+ *   paired_prob   laid out like `constraints`: n_s f32 at paired_prob + (offsets[s] - offsets[0])
+ *                 (may be NULL).  For base x the probability that x is paired, summed over ALL present
+ *                 pairs whatever min_prob is, in this order: start from +0; for d = 1 .. n-1
+ *                 ascending add p(x, x+d) if x + d < n and the pair is present, then p(x-d, x) if
+ *                 x >= d and the pair is present; one rounded f32 add each.  Not clamped.
+ *   log_partition n_seqs f32 (may be NULL)
+ * The probabilities come from the context's summation mode exactly as rnamc_bpp_batch_constrained
+ * produces them: every pair_prob has the bits of the dense triangle's cell.  Results do not depend
+ * on grouping, on the other records of the batch, on knobs or on the device.
+ * With the three arrays NULL the call only counts: pair_count (may then be NULL), *pairs_total,
+ * paired_prob and log_partition are produced, pair_start is untouched.  With arrays and
+ * pairs_cap < total: RNAMC_ERR_INVALID_ARG, pair_count and *pairs_total set, the arrays' contents
+ * unspecified (the rnamc_fold_scores idiom: call again with the total).  RNAMC_ERR_INVALID_ARG also
+ * for a NULL ctx / pool, a min_prob that is NaN, infinite or negative, only some of the three
+ * arrays, arrays without pair_start / pair_count; bad records and bad constraints fail before any
+ * device work. */
+int rnamc_bpp_batch_sparse(rnamc_ctx* ctx, uint32_t n_seqs, const uint8_t* bases,
+                           const uint64_t* offsets, const char* constraints, uint32_t max_bp_span,
+                           int uses_contra_model, int allows_short_hairpins, float min_prob,
+                           uint64_t* pair_start, uint64_t* pair_count, uint32_t* pair_i,
+                           uint32_t* pair_j, float* pair_prob, uint64_t pairs_cap,
+                           uint64_t* pairs_total, float* paired_prob, float* log_partition);
+/* The same over the pool's devices: the shards of rnamc_bpp_batch_multi_constrained
+ * (rnamc_shard_plan), each through its own context; every group of every shard claims its part of
+ * the three arrays from one shared cursor, so nothing is gathered afterwards. */
+int rnamc_bpp_batch_sparse_multi(rnamc_pool* pool, uint32_t n_seqs, const uint8_t* bases,
+                                 const uint64_t* offsets, const char* constraints,
+                                 uint32_t max_bp_span, int uses_contra_model,
+                                 int allows_short_hairpins, float min_prob, uint64_t* pair_start,
+                                 uint64_t* pair_count, uint32_t* pair_i, uint32_t* pair_j,
+                                 float* pair_prob, uint64_t pairs_cap, uint64_t* pairs_total,
+                                 float* paired_prob, float* log_partition);
+
 #ifdef __cplusplus
 }
 #endif

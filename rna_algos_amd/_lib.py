@@ -33,6 +33,7 @@ SYMBOLS = [
     "rnamc_bpp_batch_constrained", "rnamc_bpp_batch_multi_constrained",
     "rnamc_sample_batch_constrained", "rnamc_mfe_batch_constrained", "rnamc_log_partition_batch",
     "rnamc_constraint_check", "rnamc_centroid_fold_batch", "rnamc_centroid_fold_batch_multi",
+    "rnamc_bpp_batch_sparse", "rnamc_bpp_batch_sparse_multi",
 ]
 
 
@@ -171,6 +172,11 @@ def lib():
     L.rnamc_centroid_fold_batch.argtypes = [vp, C.c_uint32, vp, vp, C.c_char_p, C.c_uint32, C.c_int, C.c_int,
                                             vp, C.c_uint32, vp, vp, vp, vp, vp, vp]
     L.rnamc_centroid_fold_batch_multi.argtypes = L.rnamc_centroid_fold_batch.argtypes
+    # (ctx or pool, n_seqs, bases, offsets, constraints, max_bp_span, contra, short hairpins, min_prob,
+    # pair_start, pair_count, pair_i, pair_j, pair_prob, pairs_cap, pairs_total, paired_prob, log_partition)
+    L.rnamc_bpp_batch_sparse.argtypes = [vp, C.c_uint32, vp, vp, C.c_char_p, C.c_uint32, C.c_int, C.c_int,
+                                         C.c_float, vp, vp, vp, vp, vp, C.c_uint64, u64p, vp, vp]
+    L.rnamc_bpp_batch_sparse_multi.argtypes = L.rnamc_bpp_batch_sparse.argtypes
     _lib = L
     return L
 

@@ -8,14 +8,17 @@ reference iterates a hash map, so the order of the triples inside a record is
 unspecified there; here it is ascending (i, j).  The whole FASTA goes to the GPU as one
 batch instead of one thread-pool task per record; `-t` is accepted and ignored.
 `--constraints FILE` / `--max-bp-span L` (not in the reference) give the pair probabilities over a
-restricted structure space (bin/_constraints.py)."""
+restricted structure space (bin/_constraints.py).  `--min-bpp P` (not in the reference) writes only
+the triples with p >= P, taken from the device-compacted lists (rnamc_bpp_batch_sparse): the dense
+triangles never reach the host.  Without the flag nothing changes."""
 import argparse
+import math
 import sys
 
 import numpy as np
 
 from ..utils import FoldScoreSets, NoTablesError, read_fasta, set_default_tables
-from ..mccaskill_algo import mccaskill_algo_batch
+from ..mccaskill_algo import mccaskill_algo_batch, mccaskill_algo_batch_sparse
 from . import _constraints
 
 HEADER = ("# Format = >{RNA sequence id} {line break} {basepairing left nucleotide}, "
@@ -44,6 +47,12 @@ def probs2str(mat):
     return "".join(out)
 
 
+def sparse2str(sp):
+    """probs2str over a SparseBpp: its triples in ascending (i, j) order."""
+    order = np.lexsort((sp.j, sp.i))
+    return "".join(f"{int(sp.i[k])},{int(sp.j[k])},{fmt_f32(sp.p[k])} " for k in order)
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(prog="mccaskill_algo")
     ap.add_argument("-i", "--input_file_path", required=True)
@@ -54,9 +63,13 @@ def parse_args(argv=None):
                     help="NOT the reference's parameters: seeded synthetic tables (testing only). "
                          "Without it $RNAMC_TABLES must name a table file dumped from the "
                          "rna-ss-params crate")
+    ap.add_argument("--min-bpp", type=float, default=None, metavar="P",
+                    help="write only the pairs with probability >= P (finite, >= 0)")
     _constraints.add_args(ap)
     args = ap.parse_args(argv)
     _constraints.check_span(ap, args)
+    if args.min_bpp is not None and not (math.isfinite(args.min_bpp) and args.min_bpp >= 0):
+        ap.error("--min-bpp must be finite and >= 0")
     return args
 
 
@@ -80,12 +93,19 @@ def main(argv=None):
         except (_constraints.ConstraintFileError, OSError) as e:
             print(f"error: {e}", file=sys.stderr)
             return 2
-    mats, _ = mccaskill_algo_batch([s for _, s in recs], args.uses_contra_model, False,
-                                   fold_score_sets, cons, args.max_bp_span)
     buf = [HEADER]
-    for rna_id, m in enumerate(mats):
-        buf.append(f"\n\n>{rna_id}\n")
-        buf.append(probs2str(m))
+    if args.min_bpp is not None:
+        lists, _ = mccaskill_algo_batch_sparse([s for _, s in recs], args.uses_contra_model, False,
+                                               fold_score_sets, args.min_bpp, cons, args.max_bp_span)
+        for rna_id, sp in enumerate(lists):
+            buf.append(f"\n\n>{rna_id}\n")
+            buf.append(sparse2str(sp))
+    else:
+        mats, _ = mccaskill_algo_batch([s for _, s in recs], args.uses_contra_model, False,
+                                       fold_score_sets, cons, args.max_bp_span)
+        for rna_id, m in enumerate(mats):
+            buf.append(f"\n\n>{rna_id}\n")
+            buf.append(probs2str(m))
     with open(args.output_file_path, "w") as fh:
         fh.write("".join(buf))
     return 0

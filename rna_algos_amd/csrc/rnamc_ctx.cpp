@@ -165,6 +165,12 @@ void rnamc_ctx_destroy(rnamc_ctx* c) {
     if (c->cf_np) (void)hipFree(c->cf_np);
     if (c->cf_acc) (void)hipFree(c->cf_acc);
     if (c->st_cons) (void)hipFree(c->st_cons);
+    if (c->sp_items) (void)hipFree(c->sp_items);
+    if (c->sp_totals) (void)hipFree(c->sp_totals);
+    if (c->sp_i) (void)hipFree(c->sp_i);
+    if (c->sp_j) (void)hipFree(c->sp_j);
+    if (c->sp_p) (void)hipFree(c->sp_p);
+    if (c->sp_paired) (void)hipFree(c->sp_paired);
   }
   delete c;
 }

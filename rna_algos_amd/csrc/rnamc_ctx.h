@@ -182,6 +182,15 @@ struct rnamc_ctx {
   float* cf_acc = nullptr;
   uint64_t cf_items_cap = 0, cf_np_cap = 0, cf_acc_cap = 0;
   int64_t centroid_chunk_bytes = 0;
+  // rnamc_bpp_batch_sparse (grow-only): a group's record descriptors and totals, its staged lists
+  // (i, j, p) and paired probabilities
+  rnamc::SparseItem* sp_items = nullptr;
+  uint32_t* sp_totals = nullptr;
+  uint32_t* sp_i = nullptr;
+  uint32_t* sp_j = nullptr;
+  float* sp_p = nullptr;
+  float* sp_paired = nullptr;
+  uint64_t sp_items_cap = 0, sp_totals_cap = 0, sp_i_cap = 0, sp_j_cap = 0, sp_p_cap = 0, sp_paired_cap = 0;
 };
 
 namespace rnamc {

@@ -149,6 +149,29 @@ void launch_centroid_batch(const CentroidChunk& a, uint32_t d, uint32_t n_active
 // traceback of every item: one wave per item; n_waves a multiple of 4 (256-thread blocks)
 void launch_centroid_trace(const CentroidChunk& a, uint32_t n_waves, hipStream_t st);
 
+// thresholded sparse pair probabilities of a group (rnamc_sparse.hip).  A
+// record's packed triangle is cut into blocks of 256 consecutive cells; a cell is listed when it is
+// present (p > -0.5) and p >= min_prob.
+struct SparseItem {
+  uint64_t bpp_off;   // float offset of the record's bpp triangle in `bpp`
+  uint64_t blk_off;   // offset of its n_blocks block counts / bases in `blocks`
+  uint64_t out_off;   // offset of its list in the group's staged i / j / p arrays (fill)
+  uint64_t pp_off;    // offset of its n paired probabilities in the group's staged array
+  uint32_t n;
+  uint32_t n_blocks;  // ceil(n(n+1)/2 / 256)
+};
+// at most 65535 items a launch; max_blocks / max_n: the largest of the launch's items
+void launch_sparse_count(const SparseItem* items, uint32_t n_items, uint32_t max_blocks, const float* bpp,
+                         uint32_t* blocks, float min_prob, hipStream_t st);
+// block counts -> exclusive block bases in place; totals[x] = listed cells of item x (any number of items)
+void launch_sparse_scan(const SparseItem* items, uint32_t n_items, uint32_t* blocks, uint32_t* totals,
+                        hipStream_t st);
+void launch_sparse_fill(const SparseItem* items, uint32_t n_items, uint32_t max_blocks, const float* bpp,
+                        const uint32_t* blocks, float min_prob, uint32_t* out_i, uint32_t* out_j, float* out_p,
+                        hipStream_t st);
+void launch_sparse_paired(const SparseItem* items, uint32_t n_items, uint32_t max_n, const float* bpp,
+                          float* paired, hipStream_t st);
+
 // ---- tree-order summation mode (rnamc_tree.hip) ----
 // Dense n x n matrices with row stride ld (>= n + 32, a multiple of 32 floats), msz floats
 // each; "row" = [i * ld + j], "col" = [j * ld + i].  The outside sweep reuses four slots.

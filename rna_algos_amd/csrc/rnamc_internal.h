@@ -3,6 +3,7 @@
 #ifndef RNAMC_INTERNAL_H
 #define RNAMC_INTERNAL_H
 
+#include <atomic>
 #include <cstdint>
 #include <string>
 #include <utility>
@@ -34,6 +35,21 @@ int centroid_fold_batch_core(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* bases
                              const uint64_t* struct_offs, const uint32_t* res_idx, uint32_t* n_pairs,
                              float* expect_accuracy, float* log_partition, float* bpp,
                              const uint64_t* out_offsets);
+
+// rnamc_bpp_batch_sparse behind its two entries (rnamc_entries_sparse.cpp): the arguments of the entry after
+// bpp_batch_sparse_check, plus where sequence s writes — count, start and log partition at index
+// res_idx[s], paired probabilities at paired_prob + pp_offs[s] — and the cursor from which every
+// group claims its part of the three list arrays (shared by the shards of a pool)
+int bpp_batch_sparse_check(uint32_t n_seqs, const uint8_t* bases, const uint64_t* offsets, float min_prob,
+                           const uint64_t* pair_start, const uint64_t* pair_count, const uint32_t* pair_i,
+                           const uint32_t* pair_j, const float* pair_prob, const uint64_t* pairs_total);
+int bpp_batch_sparse_core(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* bases, const uint64_t* offsets,
+                          const char* constraints, uint32_t max_bp_span, int uses_contra_model,
+                          int allows_short_hairpins, float min_prob, const uint32_t* res_idx,
+                          const uint64_t* pp_offs, uint64_t* pair_start, uint64_t* pair_count, uint32_t* pair_i,
+                          uint32_t* pair_j, float* pair_prob, uint64_t pairs_cap, std::atomic<uint64_t>* cursor,
+                          float* paired_prob, float* log_partition);
+int bpp_batch_sparse_finish(uint64_t total, bool wants_lists, uint64_t pairs_cap, uint64_t* pairs_total);
 
 // DP matrices of one sequence inside the workspace.  Every matrix is a packed
 // upper triangle of n(n+1)/2 f32 (padded to a multiple of 64 floats):

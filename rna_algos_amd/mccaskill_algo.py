@@ -143,6 +143,77 @@ class BppMatrix:
         return m
 
 
+class SparseBpp:
+    """One sequence's thresholded pair list (rnamc_bpp_batch_sparse): numpy views `i`, `j` (u32),
+    `p` (f32) in packed-triangle order (span ascending, then i ascending), `paired_prob` (f32[n]:
+    per base the probability of being paired, over ALL pairs whatever the threshold) and `n`."""
+
+    def __init__(self, n, i, j, p, paired_prob):
+        self.n = int(n)
+        self.i, self.j, self.p = i, j, p
+        self.paired_prob = paired_prob
+
+    def __len__(self):
+        return len(self.p)
+
+    def to_dict(self):
+        """{(i, j): p}: with min_prob 0 the reference's SparseProbMat<T>."""
+        return {(int(a), int(b)): float(q) for a, b, q in zip(self.i, self.j, self.p)}
+
+    def dense(self):
+        """-> BppMatrix with absent and unlisted cells at -1."""
+        n = self.n
+        packed = np.full(bpp_len(n), -1.0, dtype=np.float32)
+        i = self.i.astype(np.int64)
+        d = self.j.astype(np.int64) - i
+        packed[d * n - d * (d - 1) // 2 + i] = self.p
+        return BppMatrix(n, packed)
+
+
+# rnamc_bpp_batch_sparse, first call: list entries allotted per nucleotide (every base pairs with
+# total probability <= 1, so a record lists at most n / min_prob pairs and in practice a few per
+# base), capped at the cells that can pair at all, sum of bpp_len(n) - n.  A call that overflows is
+# repeated ONCE with the exact total it reported.
+SPARSE_PAIRS_PER_NT = 4
+sparse_retries = 0  # calls repeated so far (diagnostics)
+
+
+def _bpp_batch_sparse(entry, handle, seqs, uses_contra_model, allows_short_hairpins, min_prob,
+                      constraints, max_bp_span):
+    """rnamc_bpp_batch_sparse / _multi on `handle` -> (list of SparseBpp, log partition f32[n_seqs])."""
+    lens, offsets, bases = _pack(seqs)
+    cons = _constraint_bytes(constraints, lens)
+    ns = len(seqs)
+    start = np.zeros(max(ns, 1), dtype=np.uint64)
+    count = np.zeros(max(ns, 1), dtype=np.uint64)
+    paired = np.zeros(max(int(offsets[-1]), 1), dtype=np.float32)
+    logz = np.empty(max(ns, 1), dtype=np.float32)
+    total = C.c_uint64(0)
+    most = int(np.sum(lens * (lens + 1) // 2 - lens))
+    cap = max(min(int(SPARSE_PAIRS_PER_NT * int(offsets[-1])), most), 1)
+    for attempt in range(2):
+        pi = np.empty(cap, dtype=np.uint32)
+        pj = np.empty(cap, dtype=np.uint32)
+        pp = np.empty(cap, dtype=np.float32)
+        status = entry(handle, ns, bases.ctypes.data, offsets.ctypes.data, cons, _span(max_bp_span),
+                       int(bool(uses_contra_model)), int(bool(allows_short_hairpins)), float(min_prob),
+                       start.ctypes.data, count.ctypes.data, pi.ctypes.data, pj.ctypes.data,
+                       pp.ctypes.data, cap, C.byref(total), paired.ctypes.data, logz.ctypes.data)
+        if status == _lib.ERR_INVALID_ARG and attempt == 0 and total.value > cap:
+            cap = int(total.value)  # too small: once more with the exact total
+            global sparse_retries
+            sparse_retries += 1
+            continue
+        _lib.check(status)
+        break
+    out = []
+    for s in range(ns):
+        a, b = int(start[s]), int(start[s]) + int(count[s])
+        out.append(SparseBpp(int(lens[s]), pi[a:b], pj[a:b], pp[a:b],
+                             paired[int(offsets[s]):int(offsets[s + 1])]))
+    return out, logz[:ns]
+
+
 # one rnamc_twoloop_score (include/rnamc.h)
 TWOLOOP_DTYPE = np.dtype([("i", "<u4"), ("j", "<u4"), ("k", "<u4"), ("l", "<u4"),
                           ("score", "<f4")])
@@ -399,6 +470,14 @@ class Context:
                                     centroid_thresholds, uses_contra_model, allows_short_hairpins,
                                     constraints, max_bp_span, return_bpp)
 
+    def bpp_batch_sparse(self, seqs, uses_contra_model, allows_short_hairpins, min_prob,
+                         constraints=None, max_bp_span=0):
+        """Pair probabilities >= min_prob of every sequence, compacted on the device
+        (rnamc_bpp_batch_sparse) -> (list of SparseBpp, log partition f32[n_seqs]).
+        constraints, max_bp_span: as bpp_batch."""
+        return _bpp_batch_sparse(_lib.lib().rnamc_bpp_batch_sparse, self._h, list(seqs), uses_contra_model,
+                                 allows_short_hairpins, min_prob, constraints, max_bp_span)
+
     def debug_fetch(self, seq_idx, which, n):
         out = np.empty((n, n), dtype=np.float32)
         _lib.check(_lib.lib().rnamc_debug_fetch(self._h, seq_idx, which, out.ctypes.data))
@@ -467,6 +546,14 @@ class Pool:
         return _centroid_fold_batch(_lib.lib().rnamc_centroid_fold_batch_multi, self._h, list(seqs),
                                     centroid_thresholds, uses_contra_model, allows_short_hairpins,
                                     constraints, max_bp_span, return_bpp)
+
+
+    def bpp_batch_sparse(self, seqs, uses_contra_model, allows_short_hairpins, min_prob,
+                         constraints=None, max_bp_span=0):
+        """As Context.bpp_batch_sparse, sharded over the pool's contexts
+        (rnamc_bpp_batch_sparse_multi)."""
+        return _bpp_batch_sparse(_lib.lib().rnamc_bpp_batch_sparse_multi, self._h, list(seqs),
+                                 uses_contra_model, allows_short_hairpins, min_prob, constraints, max_bp_span)
 
 
 def shard_plan(lengths, n_shards):
@@ -570,6 +657,17 @@ def mccaskill_algo_batch(seqs, uses_contra_model, allows_short_hairpins, fold_sc
     with _ctx_lock:
         return _pool_for(fold_score_sets).bpp_batch(list(seqs), uses_contra_model,
                                                     allows_short_hairpins, constraints, max_bp_span)
+
+
+def mccaskill_algo_batch_sparse(seqs, uses_contra_model, allows_short_hairpins, fold_score_sets,
+                                min_prob, constraints=None, max_bp_span=0):
+    """mccaskill_algo_batch returning only the pairs with p >= min_prob (0: every key of the
+    reference's SparseProbMat), compacted on the device: the dense triangles never reach the host
+    -> (list of SparseBpp, log partition f32[n_seqs])."""
+    with _ctx_lock:
+        return _pool_for(fold_score_sets).bpp_batch_sparse(list(seqs), uses_contra_model,
+                                                           allows_short_hairpins, min_prob, constraints,
+                                                           max_bp_span)
 
 
 def structure_score(seq, dot_bracket, uses_contra_model, allows_short_hairpins, fold_score_sets):

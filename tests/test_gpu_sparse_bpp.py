@@ -1,0 +1,325 @@
+"""rnamc_bpp_batch_sparse / rnamc_bpp_batch_sparse_multi on the GPU: thresholded pair lists and
+per-base paired probabilities compacted on the device.
+
+The yardstick throughout is the dense entry (rnamc_bpp_batch_constrained) on the same context and
+inputs, which the parity suite pins to the oracle; everything is compared bit for bit, no
+tolerances anywhere."""
+import os
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+# 1, 2: no cell can pair; 5, 6: the first admissible span; 22, 23: 253 and 276 cells, either side of one
+# 256-cell block (23: one block covering every diagonal); 63, 64, 65: the wave edge; 181: many blocks, top
+# blocks straddling dozens of diagonals; 300: several blocks per diagonal.  One ragged batch, shuffled.
+LENS = [65, 2, 181, 23, 5, 300, 1, 64, 22, 6, 63]
+MIN_PROBS = [0.0, 1e-3, 0.5, 2.0]
+
+
+@pytest.fixture(scope="module")
+def ctx(params):
+    from rna_algos_amd.mccaskill_algo import Context
+    c = Context(params, device=0)
+    yield c
+    c.close()
+
+
+def reset(ctx):
+    for k, v in (("summation_mode", 0), ("group_max_seqs", 8192)):
+        ctx.set(k, v)
+
+
+def batch():
+    from rna_algos_amd.workloads import synthetic_seq
+    return [synthetic_seq(n, seed=900 + n) for n in LENS]
+
+
+def sparse_raw(entry, handle, seqs, contra, min_prob, cons=None, span=0, cap=None, lists=True, two_only=False):
+    """the C entry itself -> (status, dict): per-record (i, j, p) views, counts, starts, total,
+    paired_prob per record, log partition.  cap None: a count-only call first sizes the arrays."""
+    from rna_algos_amd import _lib
+    from rna_algos_amd.mccaskill_algo import _constraint_bytes, _pack
+    import ctypes as C
+    lens, offsets, bases = _pack(seqs)
+    cb = _constraint_bytes(cons, lens)
+    ns = len(seqs)
+    start = np.full(max(ns, 1), 2 ** 63, dtype=np.uint64)
+    count = np.full(max(ns, 1), 2 ** 63, dtype=np.uint64)
+    paired = np.full(max(int(offsets[-1]), 1), np.nan, dtype=np.float32)
+    logz = np.full(max(ns, 1), np.nan, dtype=np.float32)
+    total = C.c_uint64(2 ** 63)
+    head = (handle, ns, bases.ctypes.data, offsets.ctypes.data, cb, span, int(contra), 0, float(min_prob))
+    if lists and cap is None:
+        _lib.check(entry(*head, None, count.ctypes.data, None, None, None, 0, C.byref(total), None, None))
+        cap = int(total.value)
+    n_alloc = max(int(cap or 0), 1)
+    pi = np.full(n_alloc, 0xffffffff, dtype=np.uint32)
+    pj = np.full(n_alloc, 0xffffffff, dtype=np.uint32)
+    pp = np.full(n_alloc, np.nan, dtype=np.float32)
+    if lists:
+        st = entry(*head, start.ctypes.data, count.ctypes.data, pi.ctypes.data, pj.ctypes.data,
+                   None if two_only else pp.ctypes.data, cap, C.byref(total), paired.ctypes.data, logz.ctypes.data)
+    else:
+        st = entry(*head, start.ctypes.data, count.ctypes.data, None, None, None, 0, C.byref(total),
+                   paired.ctypes.data, logz.ctypes.data)
+    res = dict(start=start[:ns], count=count[:ns], total=int(total.value), logz=logz[:ns],
+               paired=[paired[int(offsets[s]):int(offsets[s + 1])] for s in range(ns)], cap=cap)
+    if lists and st == _lib.OK:
+        res["lists"] = [(pi[int(a):int(a + c)], pj[int(a):int(a + c)], pp[int(a):int(a + c)])
+                        for a, c in zip(start[:ns], count[:ns])]
+    return st, res
+
+
+def ctx_sparse(ctx, seqs, contra, min_prob, **kw):
+    from rna_algos_amd import _lib
+    st, res = sparse_raw(_lib.lib().rnamc_bpp_batch_sparse, ctx._h, seqs, contra, min_prob, **kw)
+    assert st == _lib.OK, st
+    return res
+
+
+def filtered(packed, n, min_prob):
+    """the dense triangle's listed cells in packed order -> (i, j, p)"""
+    idx = np.nonzero((packed > -0.5) & (packed >= np.float32(min_prob)))[0]
+    starts = np.array([d * n - d * (d - 1) // 2 for d in range(n + 1)], dtype=np.int64)
+    d = np.searchsorted(starts, idx, side="right") - 1
+    i = idx - starts[d]
+    return i.astype(np.uint32), (i + d).astype(np.uint32), packed[idx]
+
+
+def replay_paired(packed, n):
+    """paired_prob in the defined f32 order: for d ascending, p(x, x+d) then p(x-d, x), one rounded add each"""
+    acc = np.zeros(n, dtype=np.float32)
+    off = n
+    for d in range(1, n):
+        row = packed[off:off + n - d]
+        add = np.where(row > -0.5, row, np.float32(0)).astype(np.float32)  # (x + 0 == x: an absent pair adds nothing)
+        acc[:n - d] = acc[:n - d] + add
+        acc[d:] = acc[d:] + add
+        off += n - d
+    return acc
+
+
+def assert_lists_equal(lists, mats, min_prob):
+    for (pi, pj, pp), m in zip(lists, mats):
+        wi, wj, wp = filtered(m.packed, m.n, min_prob)
+        assert np.array_equal(pi, wi), m.n
+        assert np.array_equal(pj, wj), m.n
+        assert np.array_equal(pp.view(np.uint32), wp.view(np.uint32)), m.n
+
+
+def assert_disjoint(res):
+    spans = sorted((int(a), int(a + c)) for a, c in zip(res["start"], res["count"]) if c)
+    for (_, hi), (lo, _) in zip(spans, spans[1:]):
+        assert hi <= lo
+    assert res["total"] == int(res["count"].sum())
+    assert all(hi <= res["cap"] for _, hi in spans)
+
+
+_dense_cache = {}
+
+
+def dense(ctx, seqs, contra, mode):
+    """the dense yardstick, once per (model, mode), shared and left unchanged"""
+    key = (contra, mode)
+    if key not in _dense_cache:
+        reset(ctx)
+        ctx.set("summation_mode", mode)
+        try:
+            _dense_cache[key] = ctx.bpp_batch(seqs, contra, False)
+        finally:
+            reset(ctx)
+    return _dense_cache[key]
+
+
+@pytest.mark.parametrize("mode", [0, 1])
+@pytest.mark.parametrize("contra", [False, True])
+def test_equals_filtered_dense(ctx, contra, mode):
+    """both models x both summation modes x four thresholds: lists, paired_prob and log_partition equal
+    the dense entry's, bit for bit"""
+    seqs = batch()
+    mats, logz = dense(ctx, seqs, contra, mode)
+    reset(ctx)
+    ctx.set("summation_mode", mode)
+    try:
+        for min_prob in MIN_PROBS:
+            res = ctx_sparse(ctx, seqs, contra, min_prob)
+            assert_lists_equal(res["lists"], mats, min_prob)
+            assert_disjoint(res)
+            assert np.array_equal(res["logz"].view(np.uint32), logz.view(np.uint32))
+            for s, m in enumerate(mats):
+                assert np.array_equal(res["paired"][s].view(np.uint32), replay_paired(m.packed, m.n).view(np.uint32)), m.n
+                if min_prob == 0.0:
+                    assert int(res["count"][s]) == int(np.sum(m.packed > -0.5))
+            if min_prob == 0.0:
+                assert res["total"] > 0
+                for n, c in zip(LENS, res["count"]):
+                    assert n > 2 or c == 0
+    finally:
+        reset(ctx)
+
+
+@pytest.mark.parametrize("case", ["groups_of_1", "groups_of_3", "reversed"])
+def test_independent_of_schedule(ctx, case):
+    seqs = batch()
+    reset(ctx)
+    base = ctx_sparse(ctx, seqs, False, 1e-3)
+    order = list(range(len(seqs)))
+    if case == "groups_of_1":
+        ctx.set("group_max_seqs", 1)
+    elif case == "groups_of_3":
+        ctx.set("group_max_seqs", 3)
+    else:
+        order.reverse()
+    try:
+        res = ctx_sparse(ctx, [seqs[x] for x in order], False, 1e-3)
+    finally:
+        reset(ctx)
+    assert_disjoint(res)
+    for pos, x in enumerate(order):
+        for a, b in zip(res["lists"][pos], base["lists"][x]):
+            assert np.array_equal(a.view(np.uint32), b.view(np.uint32)), LENS[x]
+        assert np.array_equal(res["paired"][pos].view(np.uint32), base["paired"][x].view(np.uint32))
+        assert res["logz"][pos].view(np.uint32) == base["logz"][x].view(np.uint32)
+
+
+def test_capacity_protocol(ctx):
+    from rna_algos_amd import _lib
+    import ctypes as C
+    L = _lib.lib()
+    seqs = batch()
+    reset(ctx)
+    full = ctx_sparse(ctx, seqs, False, 1e-3)
+    total = full["total"]
+    assert total > 1
+    st, cnt = sparse_raw(L.rnamc_bpp_batch_sparse, ctx._h, seqs, False, 1e-3, lists=False)
+    assert st == _lib.OK and cnt["total"] == total and np.array_equal(cnt["count"], full["count"])
+    assert np.all(cnt["start"] == 2 ** 63)  # untouched
+    for a, b in zip(cnt["paired"], full["paired"]):
+        assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
+    assert np.array_equal(cnt["logz"].view(np.uint32), full["logz"].view(np.uint32))
+    st, small = sparse_raw(L.rnamc_bpp_batch_sparse, ctx._h, seqs, False, 1e-3, cap=total - 1)
+    assert st == _lib.ERR_INVALID_ARG and small["total"] == total and np.array_equal(small["count"], full["count"])
+    st, exact = sparse_raw(L.rnamc_bpp_batch_sparse, ctx._h, seqs, False, 1e-3, cap=total)
+    assert st == _lib.OK
+    for a, b in zip(exact["lists"], full["lists"]):
+        for x, y in zip(a, b):
+            assert np.array_equal(x.view(np.uint32), y.view(np.uint32))
+    st, _ = sparse_raw(L.rnamc_bpp_batch_sparse, ctx._h, seqs, False, 1e-3, cap=total, two_only=True)
+    assert st == _lib.ERR_INVALID_ARG
+    for bad in (float("nan"), -1e-3, float("inf")):
+        st, _ = sparse_raw(L.rnamc_bpp_batch_sparse, ctx._h, seqs, False, bad, cap=total)
+        assert st == _lib.ERR_INVALID_ARG, bad
+    offsets = np.zeros(1, np.uint64)
+    tot = C.c_uint64(77)
+    assert L.rnamc_bpp_batch_sparse(ctx._h, 0, None, offsets.ctypes.data, None, 0, 0, 0, 0.0, None, None, None,
+                                    None, None, 0, C.byref(tot), None, None) == _lib.OK
+    assert tot.value == 0
+
+
+def test_constraints(ctx):
+    """80 nt with an x run, a matched bracket pair and max_bp_span = 30: no forbidden pair is listed and the
+    lists equal the filtered constrained triangle"""
+    from rna_algos_amd.workloads import synthetic_seq
+    reset(ctx)
+    seq = synthetic_seq(80, seed=80)
+    c = ["."] * 80
+    c[10:16] = "x" * 6
+    c[20], c[44] = "(", ")"
+    cons, span = ["".join(c)], 30
+    mats, logz = ctx.bpp_batch([seq], False, False, constraints=cons, max_bp_span=span)
+    for min_prob in (0.0, 1e-3):
+        res = ctx_sparse(ctx, [seq], False, min_prob, cons=cons, span=span)
+        assert_lists_equal(res["lists"], mats, min_prob)
+        assert np.array_equal(res["logz"].view(np.uint32), logz.view(np.uint32))
+        assert np.array_equal(res["paired"][0].view(np.uint32), replay_paired(mats[0].packed, 80).view(np.uint32))
+        pi, pj, _ = res["lists"][0]
+        pi, pj = pi.astype(np.int64), pj.astype(np.int64)
+        assert len(pi) > 0
+        assert np.all(pj - pi + 1 <= span)
+        assert not np.any((pi >= 10) & (pi < 16)) and not np.any((pj >= 10) & (pj < 16))
+        ends = np.isin(pi, (20, 44)) | np.isin(pj, (20, 44))
+        assert np.all((pi[ends] == 20) & (pj[ends] == 44))
+        assert not np.any((pi < 20) & (pj > 20) & (pj < 44)) and not np.any((pi > 20) & (pi < 44) & (pj > 44))
+
+
+def test_pool_equals_context(ctx, params):
+    """two contexts on device 0: per-record lists, paired_prob and log_partition equal the single-context
+    call's; a bad record fails the call before device work"""
+    from rna_algos_amd import _lib
+    from rna_algos_amd.mccaskill_algo import Pool
+    L = _lib.lib()
+    seqs = batch()
+    reset(ctx)
+    a = ctx_sparse(ctx, seqs, True, 1e-3)
+    pool = Pool(params, devices=[0, 0])
+    try:
+        st, b = sparse_raw(L.rnamc_bpp_batch_sparse_multi, pool._h, seqs, True, 1e-3)
+        assert st == _lib.OK
+        assert_disjoint(b)
+        assert np.array_equal(a["count"], b["count"]) and a["total"] == b["total"]
+        for x, y in zip(a["lists"], b["lists"]):
+            for u, v in zip(x, y):
+                assert np.array_equal(u.view(np.uint32), v.view(np.uint32))
+        for x, y in zip(a["paired"], b["paired"]):
+            assert np.array_equal(x.view(np.uint32), y.view(np.uint32))
+        assert np.array_equal(a["logz"].view(np.uint32), b["logz"].view(np.uint32))
+        bad = [s.copy() for s in seqs]
+        bad[3][1] = 9
+        st, r = sparse_raw(L.rnamc_bpp_batch_sparse_multi, pool._h, bad, True, 1e-3, cap=a["total"])
+        assert st == _lib.ERR_INVALID_BASE
+        assert np.all(np.isnan(r["logz"])) and np.all(r["count"] == 2 ** 63)  # nothing was written
+    finally:
+        pool.close()
+
+
+def test_python_mirror_and_retry(params, trnas):
+    from rna_algos_amd import mccaskill_algo as M
+    seqs = [s for _, s in trnas]
+    min_prob = 0.01
+    mats, logz = M.mccaskill_algo_batch(seqs, False, False, params)
+    sparse, logz2 = M.mccaskill_algo_batch_sparse(seqs, False, False, params, min_prob)
+    assert np.array_equal(logz.view(np.uint32), logz2.view(np.uint32))
+
+    def check(sparse):
+        for sp, m in zip(sparse, mats):
+            keep = (m.packed > -0.5) & (m.packed >= np.float32(min_prob))
+            want = np.where(keep, m.packed, np.float32(-1))
+            assert np.array_equal(sp.dense().packed.view(np.uint32), want.view(np.uint32))
+            assert sp.n == m.n and len(sp) == int(keep.sum())
+            assert sp.to_dict() == {k: v for k, v in m.sparse().items() if np.float32(v) >= np.float32(min_prob)}
+            assert np.array_equal(sp.paired_prob.view(np.uint32), replay_paired(m.packed, m.n).view(np.uint32))
+    check(sparse)
+    before, per_nt = M.sparse_retries, M.SPARSE_PAIRS_PER_NT
+    M.SPARSE_PAIRS_PER_NT = 0  # one list entry for the whole batch: the call overflows and is repeated once
+    try:
+        again, _ = M.mccaskill_algo_batch_sparse(seqs, False, False, params, min_prob)
+    finally:
+        M.SPARSE_PAIRS_PER_NT = per_nt
+    assert M.sparse_retries == before + 1
+    check(again)
+
+
+def test_cli_min_bpp(params, tmp_path):
+    """--min-bpp 0.01 writes exactly the unflagged text without the triples below 0.01"""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    fa = os.path.join(root, "tests", "golden", "sampled_trnas.fa")
+    outs = []
+    for extra in ([], ["--min-bpp", "0.01"]):
+        out = os.path.join(tmp_path, "out%d.txt" % len(outs))
+        subprocess.check_call([sys.executable, "-m", "rna_algos_amd.bin.mccaskill_algo", "--synthetic-tables", "1",
+                               "-i", fa, "-o", out] + extra, cwd=root, stderr=subprocess.DEVNULL)
+        outs.append(open(out).read())
+    want = []
+    for block in outs[0].split("\n\n"):
+        if not block.startswith(">"):
+            want.append(block)
+            continue
+        head, body = block.split("\n", 1)
+        kept = [t for t in body.split(" ") if t and np.float32(t.split(",")[2]) >= np.float32(0.01)]
+        want.append(head + "\n" + "".join(t + " " for t in kept))
+    assert outs[1] == "\n\n".join(want)
+    assert outs[1] != outs[0] and outs[1].count(",") > 0
