@@ -62,6 +62,9 @@ extern "C" {
   fn rnamc_bpp_len(n: u32) -> u64;
   fn rnamc_bpp_batch_multi(pool: *mut RnamcPool, n_seqs: u32, bases: *const u8, offsets: *const u64, uses_contra_model: c_int, allows_short_hairpins: c_int, bpp: *mut f32, out_offsets: *const u64, log_partition: *mut f32) -> c_int;
   fn rnamc_bpp_batch_sparse_multi(pool: *mut RnamcPool, n_seqs: u32, bases: *const u8, offsets: *const u64, constraints: *const c_char, max_bp_span: u32, uses_contra_model: c_int, allows_short_hairpins: c_int, min_prob: f32, pair_start: *mut u64, pair_count: *mut u64, pair_i: *mut u32, pair_j: *mut u32, pair_prob: *mut f32, pairs_cap: u64, pairs_total: *mut u64, paired_prob: *mut f32, log_partition: *mut f32) -> c_int;
+  fn rnamc_window_plan(n: u64, window: u32, stride: u32, max_bp_span: u32, n_windows: *mut u64, band: *mut u32, starts: *mut u64, starts_cap: u64) -> c_int;
+  fn rnamc_bpp_windowed(ctx: *mut RnamcCtx, bases: *const u8, n: u64, constraint: *const c_char, window: u32, stride: u32, max_bp_span: u32, uses_contra_model: c_int, allows_short_hairpins: c_int, band_prob: *mut f32, paired_prob: *mut f32, window_log_partition: *mut f32) -> c_int;
+  fn rnamc_bpp_windowed_multi(pool: *mut RnamcPool, bases: *const u8, n: u64, constraint: *const c_char, window: u32, stride: u32, max_bp_span: u32, uses_contra_model: c_int, allows_short_hairpins: c_int, band_prob: *mut f32, paired_prob: *mut f32, window_log_partition: *mut f32) -> c_int;
   fn rnamc_fold_scores(ctx: *mut RnamcCtx, bases: *const u8, n: u32, uses_contra_model: c_int, allows_short_hairpins: c_int, hairpin_scores: *mut f32, multibranch_close_scores: *mut f32, accessible_scores: *mut f32, twoloop_scores: *mut TwoloopScore, twoloop_cap: u64, twoloop_count: *mut u64) -> c_int;
   fn rnamc_fold_sums(ctx: *mut RnamcCtx, bases: *const u8, n: u32, uses_contra_model: c_int, allows_short_hairpins: c_int, sums_external: *mut f32, sums_rightmost_basepairs_external: *mut f32, sums_rightmost_basepairs_multibranch: *mut f32, sums_close: *mut f32, sums_accessible: *mut f32, sums_multibranch: *mut f32, sums_1ormore_basepairs: *mut f32) -> c_int;
   fn rnamc_sample_batch(ctx: *mut RnamcCtx, n_seqs: u32, bases: *const u8, offsets: *const u64, uses_contra_model: c_int, allows_short_hairpins: c_int, n_samples: u32, seed: u64, structs: *mut u8, log_weights: *mut f32, log_partition: *mut f32) -> c_int;
@@ -408,6 +411,53 @@ where
       basepair_probs
     })
     .collect()
+}
+
+// Windowed local folding of one sequence of any length below 2^31 (rnamc_bpp_windowed_multi; no
+// counterpart in the reference crate): every window of `window` bases (starts 0, stride, 2 stride,
+// ..., and a last window ending at the sequence's end) folded with max_bp_span (0: no limit), each
+// pair's probability averaged over the windows that contain it.  Returns (band, paired_prob,
+// band_width): band[i * band_width + d] is pair (i, i + d), -1 where no window had the pair.  The
+// index type is usize: such a sequence may be longer than u16 positions reach.
+pub fn mccaskill_algo_windowed(
+  seq: SeqSlice,
+  window: u32,
+  stride: u32,
+  max_bp_span: u32,
+  uses_contra_model: bool,
+  allows_short_hairpins: bool,
+  fold_score_sets: &FoldScoreSets,
+) -> (Vec<f32>, Vec<f32>, usize) {
+  let bases: Vec<u8> = seq.iter().map(|&x| x as u8).collect();
+  let (mut n_windows, mut band_width) = (0u64, 0u32);
+  check(
+    unsafe { rnamc_window_plan(bases.len() as u64, window, stride, max_bp_span, &mut n_windows, &mut band_width, std::ptr::null_mut(), 0) },
+    "rnamc_window_plan",
+  );
+  let mut band = vec![-1f32; bases.len() * band_width as usize];
+  let mut paired_prob = vec![0f32; bases.len()];
+  with_pool(fold_score_sets, |pool| {
+    check(
+      unsafe {
+        rnamc_bpp_windowed_multi(
+          pool,
+          bases.as_ptr(),
+          bases.len() as u64,
+          std::ptr::null(),
+          window,
+          stride,
+          max_bp_span,
+          uses_contra_model as c_int,
+          allows_short_hairpins as c_int,
+          band.as_mut_ptr(),
+          paired_prob.as_mut_ptr(),
+          std::ptr::null_mut(),
+        )
+      },
+      "rnamc_bpp_windowed_multi",
+    );
+  });
+  (band, paired_prob, band_width as usize)
 }
 
 pub fn mccaskill_algo<T>(

@@ -283,6 +283,34 @@ std::vector<SparseProbMat<T>> mccaskill_algo_batch_sparse(const Context& ctx, co
   return out;
 }
 
+// Windowed local folding of one sequence of any length below 2^31 (rnamc_bpp_windowed; no counterpart
+// in the reference): every window of `window` bases (starts 0, stride, 2 stride, ..., and a last window
+// ending at the sequence's end) folded with max_bp_span (0: no limit), each pair's probability averaged
+// over the windows that contain it.  band[i * band_width + d] is pair (i, i + d), -1 where no window had it.
+struct WindowedBpp {
+  std::vector<float> band, paired_prob, window_log_partition;
+  std::vector<uint64_t> starts;
+  uint32_t band_width = 0;
+};
+inline WindowedBpp mccaskill_algo_windowed(const Context& ctx, const Seq& seq, uint32_t window, uint32_t stride,
+                                           uint32_t max_bp_span, bool uses_contra_model,
+                                           bool allows_short_hairpins) {
+  WindowedBpp r;
+  uint64_t n_windows = 0;
+  check(rnamc_window_plan(seq.size(), window, stride, max_bp_span, &n_windows, &r.band_width, nullptr, 0));
+  r.starts.resize(n_windows);
+  check(rnamc_window_plan(seq.size(), window, stride, max_bp_span, &n_windows, &r.band_width, r.starts.data(),
+                          n_windows));
+  r.band.resize(seq.size() * r.band_width);
+  r.paired_prob.resize(seq.size());
+  r.window_log_partition.resize(n_windows);
+  check(rnamc_bpp_windowed(ctx.get(), seq.data(), seq.size(), nullptr, window, stride, max_bp_span,
+                           uses_contra_model, allows_short_hairpins, r.band.data(), r.paired_prob.data(),
+                           r.window_log_partition.data()));
+  return r;
+}
+// the same over a pool's devices: rnamc_bpp_windowed_multi (same arguments, a rnamc_pool* first)
+
 // Boltzmann sampling (rnamc_sample_batch; no counterpart in the reference): n_samples structures
 // per sequence, each drawn with probability exp(log_weight) / exp(log_partition).  Sample t of
 // sequence s is a pure function of (tables, sequence, flags, seed, s, t).

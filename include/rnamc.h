@@ -40,7 +40,9 @@ extern "C" {
  *    since, without a version change: rnamc_sample_batch, rnamc_structure_score,
  *    rnamc_mfe_batch, rnamc_bpp_batch_constrained, rnamc_bpp_batch_multi_constrained,
  *    rnamc_sample_batch_constrained, rnamc_mfe_batch_constrained, rnamc_log_partition_batch,
- *    rnamc_constraint_check, rnamc_centroid_fold_batch, rnamc_centroid_fold_batch_multi */
+ *    rnamc_constraint_check, rnamc_centroid_fold_batch, rnamc_centroid_fold_batch_multi,
+ *    rnamc_bpp_batch_sparse, rnamc_bpp_batch_sparse_multi, rnamc_window_plan, rnamc_bpp_windowed,
+ *    rnamc_bpp_windowed_multi */
 #define RNAMC_ABI_VERSION 3u
 
 /* Compile-time limits.  In the reference these are constants of rna-ss-params
@@ -359,6 +361,11 @@ typedef struct rnamc_batch_stats {
    * long sequences, never wrong).  Probed once per context and stream, ~0.2 ms
    * (rnamc_tree.hip, tree_side_stream_probe). */
   uint64_t tree_side_stream;
+  /* rnamc_bpp_windowed: the statistics above summed over the call's chunks, and the launches of its
+   * own kernels (accumulate, finalise, paired; also counted in launches_other) with, when profiling
+   * is on, their summed device time */
+  uint64_t launches_window;
+  double ms_window;
 } rnamc_batch_stats;
 int rnamc_ctx_last_stats(rnamc_ctx* ctx, rnamc_batch_stats* out);
 /* The same with the caller's idea of the struct size: copies min(out_bytes, sizeof) bytes, so a
@@ -673,6 +680,64 @@ int rnamc_bpp_batch_sparse_multi(rnamc_pool* pool, uint32_t n_seqs, const uint8_
                                  uint64_t* pair_count, uint32_t* pair_i, uint32_t* pair_j,
                                  float* pair_prob, uint64_t pairs_cap, uint64_t* pairs_total,
                                  float* paired_prob, float* log_partition);
+
+/* ------------------------------------------------------------------------- */
+/* Windowed local folding of ONE long sequence (what RNAplfold and LocalFold compute): every window
+ * of `window` bases is folded with a pair-span limit, and each pair (i, j) gets the AVERAGE of its
+ * probability over all windows that contain it.  The windows' triangles never reach the host; the
+ * sequence may be longer than a record.
+ *   bases, n      the sequence, base codes 0..3, 1 <= n < 2^31
+ *   window        W, 1 .. 65535;  stride  S >= 1;  max_bp_span  0 = no limit
+ *   Windows: n <= W: one window [0, n).  Otherwise the starts 0, S, 2S, ... while start + W <= n,
+ *   and, if the last of these ends before n, one more window at n - W.  S > W is legal: bases that
+ *   no window covers have no pairs.
+ *   Band: B = min(W, n, max_bp_span if non-zero).  Every window is folded with max_bp_span = B
+ *   exactly as rnamc_bpp_batch_constrained folds it (the context's summation mode).
+ *   constraint    NULL or n bytes over ". x < >" only: window x gets bytes [start_x, start_x + w).
+ *                 '(' ')' (brackets cannot be cut at window edges) or any other byte:
+ *                 RNAMC_ERR_INVALID_ARG before any device work, the position in rnamc_last_error().
+ *   band_prob     n * B f32, row-major: [i * B + d] for pair (i, i + d), 0 <= d < B
+ *   paired_prob   n f32 (may be NULL)
+ *   window_log_partition  n_windows f32, ln Z of every window in window order (may be NULL)
+ * Accumulation is exact and order-free.  Every present cell (p > -0.5, d >= 1) of a window's triangle
+ * contributes the integer q = min(rint((double)p * 2^44), 2^45) (to nearest, ties to even) to a signed
+ * 64-bit sum of band cell (start + i, d), and 1 to the cell's 32-bit counter of windows in which the
+ * pair was present.  Integer adds commute, and at most 65535 windows contain a cell: the sum stays
+ * below 2^62.  Then, with denom(i, d) = the number of windows with start <= i and i + d < start + w,
+ *   band_prob[i * B + d] = (float)((double)sum / ((double)denom * 2^44))    (int64 -> double to nearest)
+ * where the counter is non-zero, and -1.0f elsewhere (d = 0, i + d >= n, never present, denom = 0).
+ * The price of order-freedom is the quantum 2^-44 (5.7e-14) per window: a single-window call equals
+ * the plain bpp exactly only where p >= 2^-20, and within 2^-45 absolute below that.
+ * paired_prob[x], from the finished band in rnamc_bpp_batch_sparse's order: start from +0; for
+ * d = 1 .. B-1 ascending add band(x, d) if present, then band(x - d, d) if x >= d and present; one
+ * rounded f32 add each, not clamped.
+ * Results do not depend on grouping, on the group knobs, on "window_chunk_nt" or on the number of
+ * devices (in summation mode 1 the sweep picks its form per staged call, "tree_lane_min_nt", as it
+ * does for rnamc_bpp_batch_constrained on the same records: there the chunk is part of the input).
+ * Knob "window_chunk_nt" (rnamc_ctx_set): nucleotides of windows that go through one staged call of
+ * the sweep, default 64 Mi, never less than one window: the window list is materialised chunk by
+ * chunk, so host and staging memory stay bounded whatever n is.
+ * RNAMC_ERR_INVALID_ARG for a NULL ctx / pool / bases / band_prob, window == 0, stride == 0,
+ * window > 65535, n >= 2^31; RNAMC_ERR_EMPTY_SEQ for n == 0; RNAMC_ERR_INVALID_BASE as elsewhere;
+ * all before any device work.  RNAMC_ERR_OOM when the accumulators (12 bytes per band cell) or the
+ * band do not fit the device. */
+
+/* Host only, no device: the window list and band width of a call.  *n_windows (never NULL) and
+ * *band (may be NULL) are always set; starts (may be NULL) receives the n_windows window starts,
+ * RNAMC_ERR_INVALID_ARG when starts_cap is too small (the count still set). */
+int rnamc_window_plan(uint64_t n, uint32_t window, uint32_t stride, uint32_t max_bp_span,
+                      uint64_t* n_windows, uint32_t* band, uint64_t* starts, uint64_t starts_cap);
+int rnamc_bpp_windowed(rnamc_ctx* ctx, const uint8_t* bases, uint64_t n, const char* constraint,
+                       uint32_t window, uint32_t stride, uint32_t max_bp_span, int uses_contra_model,
+                       int allows_short_hairpins, float* band_prob, float* paired_prob,
+                       float* window_log_partition);
+/* The same over the pool's devices: the window list is cut into shards (rnamc_shard_plan), each
+ * context accumulates its shard, the shards' integer sums and counters are added on the host, and
+ * the pool's first context finalises: bit-identical to the single-context entry. */
+int rnamc_bpp_windowed_multi(rnamc_pool* pool, const uint8_t* bases, uint64_t n, const char* constraint,
+                             uint32_t window, uint32_t stride, uint32_t max_bp_span,
+                             int uses_contra_model, int allows_short_hairpins, float* band_prob,
+                             float* paired_prob, float* window_log_partition);
 
 #ifdef __cplusplus
 }

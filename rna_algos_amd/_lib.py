@@ -34,6 +34,7 @@ SYMBOLS = [
     "rnamc_sample_batch_constrained", "rnamc_mfe_batch_constrained", "rnamc_log_partition_batch",
     "rnamc_constraint_check", "rnamc_centroid_fold_batch", "rnamc_centroid_fold_batch_multi",
     "rnamc_bpp_batch_sparse", "rnamc_bpp_batch_sparse_multi",
+    "rnamc_window_plan", "rnamc_bpp_windowed", "rnamc_bpp_windowed_multi",
 ]
 
 
@@ -56,6 +57,7 @@ class BatchStats(C.Structure):
         ("launches_outside_small", C.c_uint64),
         ("ms_outside_main", C.c_double), ("ms_outside_tail", C.c_double),
         ("ms_outside_small", C.c_double), ("tree_side_stream", C.c_uint64),
+        ("launches_window", C.c_uint64), ("ms_window", C.c_double),
     ]
 
 
@@ -177,6 +179,13 @@ def lib():
     L.rnamc_bpp_batch_sparse.argtypes = [vp, C.c_uint32, vp, vp, C.c_char_p, C.c_uint32, C.c_int, C.c_int,
                                          C.c_float, vp, vp, vp, vp, vp, C.c_uint64, u64p, vp, vp]
     L.rnamc_bpp_batch_sparse_multi.argtypes = L.rnamc_bpp_batch_sparse.argtypes
+    # (n, window, stride, max_bp_span, n_windows, band, starts, starts_cap)
+    L.rnamc_window_plan.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, u64p, u32p, vp, C.c_uint64]
+    # (ctx or pool, bases, n, constraint, window, stride, max_bp_span, contra, short hairpins, band_prob,
+    # paired_prob, window_log_partition)
+    L.rnamc_bpp_windowed.argtypes = [vp, vp, C.c_uint64, C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int,
+                                     C.c_int, vp, vp, vp]
+    L.rnamc_bpp_windowed_multi.argtypes = L.rnamc_bpp_windowed.argtypes
     _lib = L
     return L
 

@@ -171,6 +171,12 @@ void rnamc_ctx_destroy(rnamc_ctx* c) {
     if (c->sp_j) (void)hipFree(c->sp_j);
     if (c->sp_p) (void)hipFree(c->sp_p);
     if (c->sp_paired) (void)hipFree(c->sp_paired);
+    if (c->wn_items) (void)hipFree(c->wn_items);
+    if (c->wn_sum) (void)hipFree(c->wn_sum);
+    if (c->wn_cnt) (void)hipFree(c->wn_cnt);
+    if (c->wn_band) (void)hipFree(c->wn_band);
+    if (c->wn_paired) (void)hipFree(c->wn_paired);
+    for (hipEvent_t e : c->wn_events) (void)hipEventDestroy(e);
   }
   delete c;
 }
@@ -246,6 +252,8 @@ int rnamc_ctx_set(rnamc_ctx* c, const char* name, int64_t value) {
     c->group_ws_user = true;
   } else if (k == "centroid_chunk_bytes" && value >= 0) {
     c->centroid_chunk_bytes = value;
+  } else if (k == "window_chunk_nt" && value >= 1) {
+    c->window_chunk_nt = value;
   } else if (k == "block_threads" && value >= 64 && value <= 256 && value % 64 == 0) {
     // (the sweep kernels are compiled with __launch_bounds__(256))
     c->block_threads = value;

@@ -191,6 +191,17 @@ struct rnamc_ctx {
   float* sp_p = nullptr;
   float* sp_paired = nullptr;
   uint64_t sp_items_cap = 0, sp_totals_cap = 0, sp_i_cap = 0, sp_j_cap = 0, sp_p_cap = 0, sp_paired_cap = 0;
+  // rnamc_bpp_windowed (grow-only): a chunk's window descriptors, the call's integer accumulators
+  // ([d * n + i]), its band ([i * band + d]) and paired probabilities.  window_chunk_nt: nucleotides
+  // of windows that go through one staged call of the sweep (never less than one window)
+  rnamc::WindowItem* wn_items = nullptr;
+  int64_t* wn_sum = nullptr;
+  uint32_t* wn_cnt = nullptr;
+  float* wn_band = nullptr;
+  float* wn_paired = nullptr;
+  uint64_t wn_items_cap = 0, wn_sum_cap = 0, wn_cnt_cap = 0, wn_band_cap = 0, wn_paired_cap = 0;
+  std::vector<hipEvent_t> wn_events;  // profiling: a pair around every run of window kernels
+  int64_t window_chunk_nt = 64ll << 20;
 };
 
 namespace rnamc {

@@ -172,6 +172,26 @@ void launch_sparse_fill(const SparseItem* items, uint32_t n_items, uint32_t max_
 void launch_sparse_paired(const SparseItem* items, uint32_t n_items, uint32_t max_n, const float* bpp,
                           float* paired, hipStream_t st);
 
+// windowed local folding (rnamc_window.hip): the triangles of a group of
+// windows, all of length w, summed as integers into the band accumulators of the whole sequence
+struct WindowItem {
+  uint64_t bpp_off;  // float offset of the window's bpp triangle in `bpp`
+  uint64_t start;    // its first base in the sequence
+};
+// the call's window list: n_grid windows at 0, stride, 2 stride, ..., and with has_last one more
+// at n - w (off the grid); sum and cnt hold [d * n + i], the band [i * band + d]
+struct WindowGeom {
+  uint64_t n, n_grid;
+  uint32_t w, stride, band, has_last;
+};
+// at most 65535 items a launch
+void launch_window_accumulate(const WindowItem* items, uint32_t n_items, const float* bpp, uint32_t w, uint32_t band,
+                              uint64_t n_total, int64_t* sum, uint32_t* cnt, hipStream_t st);
+void launch_window_finalize(const WindowGeom& g, const int64_t* sum, const uint32_t* cnt, float* band_out,
+                            hipStream_t st);
+void launch_window_paired(const WindowGeom& g, const int64_t* sum, const uint32_t* cnt, float* paired,
+                          hipStream_t st);
+
 // ---- tree-order summation mode (rnamc_tree.hip) ----
 // Dense n x n matrices with row stride ld (>= n + 32, a multiple of 32 floats), msz floats
 // each; "row" = [i * ld + j], "col" = [j * ld + i].  The outside sweep reuses four slots.

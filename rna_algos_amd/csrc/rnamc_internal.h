@@ -51,6 +51,32 @@ int bpp_batch_sparse_core(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* bases, c
                           float* paired_prob, float* log_partition);
 int bpp_batch_sparse_finish(uint64_t total, bool wants_lists, uint64_t pairs_cap, uint64_t* pairs_total);
 
+// rnamc_bpp_windowed behind its two entries (rnamc_entries_window.cpp).  The window list of a call:
+// n_grid windows at 0, stride, 2 stride, ..., and with has_last one more at n - w.
+struct WindowPlan {
+  uint64_t n = 0, n_windows = 0, n_grid = 0;
+  uint32_t w = 0, stride = 0, band = 0, has_last = 0;
+  uint64_t start(uint64_t x) const { return x < n_grid ? x * stride : n - w; }
+};
+// the plan of (n, window, stride, max_bp_span): RNAMC_ERR_EMPTY_SEQ / RNAMC_ERR_INVALID_ARG as the entry
+int window_plan_of(uint64_t n, uint32_t window, uint32_t stride, uint32_t max_bp_span, WindowPlan* out);
+// every check of the entry that needs no context: pointers, the plan, bases, the constraint's bytes
+int bpp_windowed_check(const uint8_t* bases, uint64_t n, const char* constraint, uint32_t window, uint32_t stride,
+                       uint32_t max_bp_span, const float* band_prob, WindowPlan* out);
+// The three below run with c->mu HELD by the caller and the context's device current (the
+// accumulators live in the context from the first of them to the last).
+// zero the context's accumulators and add windows [first, first + count) into them, chunk by chunk;
+// window_log_partition (may be NULL) is the call's whole array
+int bpp_windowed_accumulate(rnamc_ctx* c, const WindowPlan& wp, const uint8_t* bases, const char* constraint,
+                            uint64_t first, uint64_t count, int uses_contra_model, int allows_short_hairpins,
+                            float* window_log_partition);
+// the context's accumulators to the host (band * n entries each, [d * n + i])
+int bpp_windowed_fetch(rnamc_ctx* c, const WindowPlan& wp, int64_t* sum, uint32_t* cnt);
+// finalise and paired kernels and the copies to the host; sum / cnt: host totals to upload first
+// (both NULL: the context's own accumulators as bpp_windowed_accumulate left them)
+int bpp_windowed_finish(rnamc_ctx* c, const WindowPlan& wp, const int64_t* sum, const uint32_t* cnt,
+                        float* band_prob, float* paired_prob);
+
 // DP matrices of one sequence inside the workspace.  Every matrix is a packed
 // upper triangle of n(n+1)/2 f32 (padded to a multiple of 64 floats):
 //  - "diag-major": cell (i,j) at  d*n - d(d-1)/2 + i  with d = j-i.  A lane that

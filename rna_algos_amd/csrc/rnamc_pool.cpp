@@ -22,6 +22,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "rnamc_ctx.h"
 #include "rnamc_internal.h"
 
 struct rnamc_pool {
@@ -449,6 +450,97 @@ int rnamc_bpp_batch_sparse_multi(rnamc_pool* p, uint32_t n_seqs, const uint8_t* 
       return sh.status;
     }
   return rnamc::bpp_batch_sparse_finish(cursor.load(), pair_i != nullptr, pairs_cap, pairs_total);
+}
+
+// rnamc_bpp_windowed over the pool: the window list cut into shards (equal windows: contiguous bands of
+// equal size), each context accumulating its shard into its own integer sums and counters; these are added
+// on the host — integer adds, any order — and the pool's first context finalises the totals: the bits of
+// the single-context entry.
+int rnamc_bpp_windowed_multi(rnamc_pool* p, const uint8_t* bases, uint64_t n, const char* constraint,
+                             uint32_t window, uint32_t stride, uint32_t max_bp_span, int uses_contra_model,
+                             int allows_short_hairpins, float* band_prob, float* paired_prob,
+                             float* window_log_partition) {
+  if (!p) return RNAMC_ERR_INVALID_ARG;
+  rnamc::WindowPlan wp;
+  if (int rc = rnamc::bpp_windowed_check(bases, n, constraint, window, stride, max_bp_span, band_prob, &wp))
+    return rc;
+  if (p->ctxs.empty()) return RNAMC_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> lock(p->mu);
+  const uint32_t n_shards = static_cast<uint32_t>(std::min<uint64_t>(p->ctxs.size(), wp.n_windows));
+  const uint64_t cells = static_cast<uint64_t>(wp.band) * wp.n;
+  struct Shard {
+    uint64_t first = 0, count = 0;
+    std::vector<int64_t> sum;
+    std::vector<uint32_t> cnt;
+    int status = RNAMC_OK;
+    std::string error;
+  };
+  std::vector<Shard> shards(n_shards);
+  try {  // nothing may throw across the C boundary
+    // the plan of rnamc_shard_plan over the windows as records of w bases (the list's order is kept)
+    const uint32_t nw = static_cast<uint32_t>(wp.n_windows);  // (n < 2^31: it fits)
+    std::vector<uint64_t> offs(static_cast<size_t>(nw) + 1);
+    for (uint64_t x = 0; x <= nw; x++) offs[x] = x * wp.w;
+    std::vector<uint32_t> shard_of(nw);
+    plan(nw, offs.data(), n_shards, shard_of.data(), nullptr);
+    for (uint32_t x = 0; x < nw; x++) {
+      Shard& sh = shards[shard_of[x]];
+      if (sh.count == 0) sh.first = x;
+      sh.count++;
+    }
+    if (n_shards > 1)
+      for (Shard& sh : shards) {
+        sh.sum.resize(cells);
+        sh.cnt.resize(cells);
+      }
+  } catch (const std::exception&) {
+    rnamc::set_last_error("rnamc_bpp_windowed_multi: no host memory");
+    return RNAMC_ERR_OOM;
+  }
+  auto work = [&](uint32_t k) {
+    Shard& sh = shards[k];
+    rnamc_ctx* c = p->ctxs[k];
+    std::unique_lock<std::mutex> ctx_lock(c->mu);
+    rnamc::DeviceGuard guard(c->device);
+    if (!guard.ok) {
+      sh.status = RNAMC_ERR_NO_DEVICE;
+      return;
+    }
+    sh.status = rnamc::bpp_windowed_accumulate(c, wp, bases, constraint, sh.first, sh.count, uses_contra_model,
+                                               allows_short_hairpins, window_log_partition);
+    if (sh.status == RNAMC_OK && n_shards > 1)
+      sh.status = rnamc::bpp_windowed_fetch(c, wp, sh.sum.data(), sh.cnt.data());
+    if (sh.status) {
+      sh.error = rnamc_last_error();  // (thread-local: carry it to the caller's thread)
+      (void)hipStreamSynchronize(c->own_stream);
+    }
+  };
+  std::vector<std::thread> pool;
+  for (uint32_t k = 1; k < n_shards; k++) {
+    try {
+      pool.emplace_back(work, k);
+    } catch (...) {  // no thread: this shard runs on the caller's thread below
+      work(k);
+    }
+  }
+  work(0);
+  for (std::thread& t : pool) t.join();
+  for (const Shard& sh : shards)
+    if (sh.status) {
+      rnamc::set_last_error(sh.error);
+      return sh.status;
+    }
+  for (uint32_t k = 1; k < n_shards; k++)
+    for (uint64_t x = 0; x < cells; x++) {
+      shards[0].sum[x] += shards[k].sum[x];
+      shards[0].cnt[x] += shards[k].cnt[x];
+    }
+  rnamc_ctx* c = p->ctxs[0];
+  std::unique_lock<std::mutex> ctx_lock(c->mu);
+  rnamc::DeviceGuard guard(c->device);
+  if (!guard.ok) return RNAMC_ERR_NO_DEVICE;
+  return rnamc::bpp_windowed_finish(c, wp, n_shards > 1 ? shards[0].sum.data() : nullptr,
+                                    n_shards > 1 ? shards[0].cnt.data() : nullptr, band_prob, paired_prob);
 }
 
 }  // extern "C"

@@ -214,6 +214,63 @@ def _bpp_batch_sparse(entry, handle, seqs, uses_contra_model, allows_short_hairp
     return out, logz[:ns]
 
 
+class WindowedBpp:
+    """Result of windowed local folding (rnamc_bpp_windowed): `band` is an (N, B) f32 view,
+    band[i, d] = the probability of pair (i, i + d) averaged over the windows that contain it (-1:
+    no such pair); `paired_prob` f32[N]; `window_log_z` f32[n_windows]; `starts` u64[n_windows]."""
+
+    def __init__(self, band, paired_prob, window_log_z, starts):
+        self.band = band
+        self.n, self.band_width = int(band.shape[0]), int(band.shape[1])
+        self.paired_prob = paired_prob
+        self.window_log_z = window_log_z
+        self.starts = starts
+
+    def pairs(self, min_prob=0.0):
+        """(i, j, p) arrays of the present pairs with p >= min_prob, ordered by span, then i."""
+        keep = (self.band > -0.5) & (self.band >= np.float32(min_prob))
+        d, i = np.nonzero(keep.T)
+        return i.astype(np.int64), (i + d).astype(np.int64), self.band[i, d]
+
+    def to_dict(self, min_prob=0.0):
+        """{(i, j): p} of `pairs(min_prob)`."""
+        return {(int(a), int(b)): float(q) for a, b, q in zip(*self.pairs(min_prob))}
+
+
+def window_plan(n, window, stride=1, max_bp_span=0):
+    """rnamc_window_plan (host only, no device): the window starts (u64 array) and the band width of
+    a windowed call -> (starts, band)."""
+    head = (int(n), int(window), int(stride), _span(max_bp_span))
+    if not (0 <= head[0] < 2 ** 64 and 0 <= head[1] < 2 ** 32 and 0 <= head[2] < 2 ** 32):
+        raise _lib.RnamcError(_lib.ERR_INVALID_ARG, "window_plan: argument out of range")
+    count, band = C.c_uint64(0), C.c_uint32(0)
+    _lib.check(_lib.lib().rnamc_window_plan(*head, C.byref(count), C.byref(band), None, 0))
+    starts = np.empty(max(count.value, 1), dtype=np.uint64)
+    _lib.check(_lib.lib().rnamc_window_plan(*head, C.byref(count), C.byref(band), starts.ctypes.data,
+                                            count.value))
+    return starts[:count.value], int(band.value)
+
+
+def _bpp_windowed(entry, handle, seq, window, uses_contra_model, allows_short_hairpins, stride, max_bp_span,
+                  constraint):
+    """rnamc_bpp_windowed / _multi on `handle` -> WindowedBpp"""
+    seq = np.ascontiguousarray(seq, dtype=np.uint8)
+    n = int(seq.shape[0])
+    starts, band = window_plan(n, window, stride, max_bp_span)
+    cons = None
+    if constraint is not None:
+        cons = constraint.encode("ascii", errors="replace") if isinstance(constraint, str) else bytes(constraint)
+        if len(cons) != n:
+            raise _lib.RnamcError(_lib.ERR_INVALID_ARG, f"constraint has length {len(cons)}, the sequence {n}")
+    out = np.empty((n, band), dtype=np.float32)
+    paired = np.empty(n, dtype=np.float32)
+    logz = np.empty(len(starts), dtype=np.float32)
+    _lib.check(entry(handle, seq.ctypes.data, n, cons, int(window), int(stride), _span(max_bp_span),
+                     int(bool(uses_contra_model)), int(bool(allows_short_hairpins)), out.ctypes.data,
+                     paired.ctypes.data, logz.ctypes.data))
+    return WindowedBpp(out, paired, logz, starts)
+
+
 # one rnamc_twoloop_score (include/rnamc.h)
 TWOLOOP_DTYPE = np.dtype([("i", "<u4"), ("j", "<u4"), ("k", "<u4"), ("l", "<u4"),
                           ("score", "<f4")])
@@ -478,6 +535,14 @@ class Context:
         return _bpp_batch_sparse(_lib.lib().rnamc_bpp_batch_sparse, self._h, list(seqs), uses_contra_model,
                                  allows_short_hairpins, min_prob, constraints, max_bp_span)
 
+    def bpp_windowed(self, seq, window, uses_contra_model, allows_short_hairpins, stride=1, max_bp_span=0,
+                     constraint=None):
+        """Windowed local folding of one (long) sequence (rnamc_bpp_windowed): every window of
+        `window` bases folded with the span limit, each pair's probability averaged over the windows
+        that contain it -> WindowedBpp.  constraint: None or one string over ". x < >"."""
+        return _bpp_windowed(_lib.lib().rnamc_bpp_windowed, self._h, seq, window, uses_contra_model,
+                             allows_short_hairpins, stride, max_bp_span, constraint)
+
     def debug_fetch(self, seq_idx, which, n):
         out = np.empty((n, n), dtype=np.float32)
         _lib.check(_lib.lib().rnamc_debug_fetch(self._h, seq_idx, which, out.ctypes.data))
@@ -554,6 +619,13 @@ class Pool:
         (rnamc_bpp_batch_sparse_multi)."""
         return _bpp_batch_sparse(_lib.lib().rnamc_bpp_batch_sparse_multi, self._h, list(seqs),
                                  uses_contra_model, allows_short_hairpins, min_prob, constraints, max_bp_span)
+
+    def bpp_windowed(self, seq, window, uses_contra_model, allows_short_hairpins, stride=1, max_bp_span=0,
+                     constraint=None):
+        """As Context.bpp_windowed, the window list sharded over the pool's contexts
+        (rnamc_bpp_windowed_multi): the same bits."""
+        return _bpp_windowed(_lib.lib().rnamc_bpp_windowed_multi, self._h, seq, window, uses_contra_model,
+                             allows_short_hairpins, stride, max_bp_span, constraint)
 
 
 def shard_plan(lengths, n_shards):
@@ -668,6 +740,18 @@ def mccaskill_algo_batch_sparse(seqs, uses_contra_model, allows_short_hairpins, 
         return _pool_for(fold_score_sets).bpp_batch_sparse(list(seqs), uses_contra_model,
                                                            allows_short_hairpins, min_prob, constraints,
                                                            max_bp_span)
+
+
+def mccaskill_algo_windowed(seq, window, uses_contra_model, allows_short_hairpins, fold_score_sets,
+                            stride=1, max_bp_span=0, constraint=None):
+    """Windowed local folding of one sequence of any length below 2^31 (RNAplfold / LocalFold): every
+    window of `window` bases (starts 0, stride, 2 stride, ..., and one last window ending at the
+    sequence's end) folded with max_bp_span, each pair's probability averaged over the windows that
+    contain it, over the process's devices -> WindowedBpp.  The windows' triangles stay on the
+    device; the result is the (N, band) array."""
+    with _ctx_lock:
+        return _pool_for(fold_score_sets).bpp_windowed(seq, window, uses_contra_model, allows_short_hairpins,
+                                                       stride, max_bp_span, constraint)
 
 
 def structure_score(seq, dot_bracket, uses_contra_model, allows_short_hairpins, fold_score_sets):
