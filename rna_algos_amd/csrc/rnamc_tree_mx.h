@@ -8,13 +8,33 @@
 // slots are the quarter-rate transcendentals).  Here the exponentials are taken per OPERAND ELEMENT
 // — once for the 32 cells of a tile row or column that use it — and a term is one multiply-add of
 // v_mfma_f32_32x32x2_f32 (f32 in, f32 accumulate: exact f32 products, a k-ordered fmaf chain, denormals
-// kept; MI355X guide, "FP32-input MFMA").  What makes that safe in f32 is the scale: not one per
-// matrix (ln-values span thousands of nats over a row) but one per operand row and CHUNK of 32 k,
-// an integer power of two 2^E with the chunk's largest factor in (2^47, 2^48]: factors of a chunk
-// keep full precision down to 2^-126, i.e. while they lie within 120 nats of the chunk's maximum
-// (sums_1ormore_basepairs grows by at most a stacked pair's ~6 nats per base), products reach 2^96
-// at most, and a chunk's partial sum joins the cell's running (exponent, sum) pair by two v_ldexp
-// — no transcendental per cell either.
+// kept; MI355X guide, "FP32-input MFMA").  The scale: not one per matrix (ln-values span thousands of
+// nats over a row) but one per operand row and CHUNK of 32 k, an integer power of two 2^E with the
+// chunk's largest factor in (2^47, 2^48]; products reach 2^96 at most, and a chunk's partial sum joins
+// the cell's running (exponent, sum) pair by two v_ldexp — no transcendental per cell either.
+//
+// What a scale per chunk can lose, and how the kernel notices.  A factor keeps full precision down to
+// 2^-126, i.e. within 174 bits = 120.6 nats of its row's chunk maximum, and is gone (below the
+// smallest denormal) after 197 bits = 136.5 nats; a PRODUCT is normal only while its two factors
+// together lie within 96 + 126 = 222 bits = 153.9 nats of their maxima.  Rows of random sequences
+// spread over 33 nats within a chunk (61 with 5.5-nat stacks), but along a run of one base that two
+// helices share, sums_1ormore_basepairs rises and its partner falls by a stacked pair's 4 - 5.5 nats
+// per k: 130 - 170 nats over a chunk, and the terms that carry the sum sit that far below BOTH maxima
+// — every product of such a chunk underflows (measured: ln Z off by 1.4, pair probabilities by 0.6).
+// No per-chunk test is needed to catch it.  Every term that was lost or rounded coarsely had a factor
+// below 2^-126 beside one of at most 2^48, or was a product below 2^-126: under 2^-78 in units of its
+// chunk's 2^(Ea + Eb).  A cell's running exponent is the LARGEST Ea + Eb of its chunks, whether or not
+// they contributed, so in the cell's final (exponent, sum) pair everything lost is below
+// 2^11 * 32 * 2^-78 = 2^-62 (at most 2^11 chunks a row, 32 terms a chunk): a sum of at least
+// kMxFloor = 2^-36 is exact to 2^-26, f32's own rounding.  A stored cell whose sum is smaller (its
+// terms lie more than 96 + 36 = 132 bits = 91 nats below the best chunk's maxima; an exponent of
+// kMxNone says that every chunk had an operand row without a finite element: nothing to lose) sends
+// its whole tile — a wave-uniform ballot for a tile per wave, a workgroup vote where four waves share
+// one — through the sums again in the exact form: one k per MFMA step, every element its own power
+// of two, factors in (2^47, 2^48] and products in (2^94, 2^96] whatever the operands do, a merge per
+// k instead of per chunk (about ten times the work; tiles of random sequences never take it, their
+// terms stay within 66 nats).  Both forms are deterministic, and so is the choice: it depends on the
+// values alone.
 //
 // Shape: a workgroup owns one 32 x 32 tile of cells in (i, j) — rows i0 .. i0+31, columns
 // j0 = i0 + dlo + 32 c .. — of the band's parallelogram (32 rows need 31 + band width columns: three
@@ -42,6 +62,7 @@ typedef int i32x4 __attribute__((ext_vector_type(4)));
 constexpr int kMxWaves = 4;   // k slices of one tile
 constexpr int kMxBias = 48;   // a chunk's largest factor lies in (2^47, 2^48]
 constexpr int kMxNone = -(1 << 28);  // exponent of an operand row without a finite element / of an empty sum
+constexpr float kMxFloor = 0x1p-36f;  // a cell's final sum below this may have lost terms to underflow (header)
 constexpr float kL2Ehi = 1.4426950216293335f;  // float(log2 e)
 constexpr float kL2Elo = 1.9259629911e-8f;     // log2 e - kL2Ehi
 constexpr float kLn2hi = 0.693359375f;         // 355 / 512: integer * kLn2hi is exact below 2^15
@@ -83,6 +104,18 @@ __device__ __forceinline__ int mx_scale(float (&v)[16], uint32_t lane) {
 #pragma unroll
   for (int e = 0; e < 16; e++) v[e] = ex2(__builtin_fmaf(v[e] - ms, kL2Ehi, c));
   return has ? static_cast<int>(ef) - kMxBias : kMxNone;
+}
+
+// one element as its own factor 2^(v log2 e - E) in (2^47, 2^48] (0 and kMxNone for -inf): mx_scale's
+// arithmetic for a row of one
+__device__ __forceinline__ float mx_scale1(float v, int& E) {
+  const bool has = v > kNegInf;
+  const float ms = has ? v : 0.f;
+  const float lo = ms * kL2Elo;
+  const float ef = __builtin_ceilf(__builtin_fmaf(ms, kL2Ehi, lo));
+  const float c = (__builtin_fmaf(ms, kL2Ehi, -ef) + lo) + static_cast<float>(kMxBias);
+  E = has ? static_cast<int>(ef) - kMxBias : kMxNone;
+  return has ? ex2(c) : 0.f;
 }
 
 // KS = 4: the workgroup's four waves share one tile (k slices, merged through LDS) — few tiles, long k ranges:
@@ -157,13 +190,64 @@ k_tree_mid_mx(TreeBatch b, uint32_t dlo, uint32_t dhi, uint32_t thr, int outside
   // the cells this lane's accumulators stand for: column j0 + r, rows i0 + 8 g + 4 h + t (reg = 4 g + t)
   int em[16];
   float sm[16];
+  // a chunk's (or, in the exact form, a k's) products join the running pairs: c in units of 2^(Ea(row) + eb),
+  // the rows' exponents through the wave's own 128 bytes of LDS (written by the half `src`)
+  auto join = [&](const f32x16& c, int ea, int eb, int src) {
+    __builtin_amdgcn_wave_barrier();
+    if (h == src) ea_lds[wave][r] = ea;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
 #pragma unroll
-  for (int x = 0; x < 16; x++) {
-    em[x] = kMxNone;
-    sm[x] = 0.f;
-  }
-  if (klo <= khi) {
+    for (int g = 0; g < 4; g++) {
+      const i32x4 e4 = *reinterpret_cast<const i32x4*>(&ea_lds[wave][8 * g + 4 * h]);
+#pragma unroll
+      for (int t = 0; t < 4; t++) {
+        const int x = 4 * g + t;
+        const int M = e4[t] + eb;
+        const int mn = max(em[x], M);
+        sm[x] = __builtin_ldexpf(sm[x], em[x] - mn) + __builtin_ldexpf(c[x], M - mn);
+        em[x] = mn;
+      }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+  };
+  auto accumulate = [&](const bool exact) {
+#pragma unroll
+    for (int x = 0; x < 16; x++) {
+      em[x] = kMxNone;
+      sm[x] = 0.f;
+    }
+    if (klo > khi) return;
     const int qlo = klo >> 5, qhi = khi >> 5;
+    if (exact) {
+      // (no unrolling, an element per lane and step straight from memory, the next step's in flight)
+      auto element = [&](const float* __restrict__ p, int k, int lo, int hi) { return k >= lo && k <= hi ? p[k] : kNegInf; };
+      for (int qq = qlo + (KS == 1 ? 0 : static_cast<int>(wave)); qq <= qhi; qq += KS) {
+        const int kb = 32 * qq + 16 * h;
+        float va = element(pa, kb, alo, ahi), vb = element(pb, kb, blo, bhi);
+#pragma unroll 1
+        for (int e = 0; e < 16; e++) {
+          const float na = e < 15 ? element(pa, kb + e + 1, alo, ahi) : kNegInf;
+          const float nb = e < 15 ? element(pb, kb + e + 1, blo, bhi) : kNegInf;
+          int ea, eb;
+          const float fa = mx_scale1(va, ea), fb = mx_scale1(vb, eb);
+#pragma unroll 1
+          for (int src = 0; src < 2; src++) {  // k = 32 qq + 16 src + e: the half `src` holds it
+            // (the step's other k: its A factor 0, its B factor finite, the product 0)
+            const int ebs = __builtin_amdgcn_ds_bpermute(static_cast<int>((static_cast<uint32_t>(r) + 32u * static_cast<uint32_t>(src)) << 2), eb);
+            f32x16 c;
+#pragma unroll
+            for (int x = 0; x < 16; x++) c[x] = 0.f;
+            c = __builtin_amdgcn_mfma_f32_32x32x2f32(h == src ? fa : 0.f, fb, c, 0, 0, 0);
+            join(c, ea, ebs, src);
+          }
+          va = na;
+          vb = nb;
+        }
+      }
+      return;
+    }
     float ra[16], rb[16];
     bool inner = false;
     auto fetch = [&](int qq) {
@@ -195,27 +279,17 @@ k_tree_mid_mx(TreeBatch b, uint32_t dlo, uint32_t dhi, uint32_t thr, int outside
       for (int x = 0; x < 16; x++) c[x] = 0.f;
 #pragma unroll
       for (int e = 0; e < 16; e++) c = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[e], fb[e], c, 0, 0, 0);
-      // row exponents of the accumulator's 16 rows: through the wave's own 128 bytes of LDS
-      __builtin_amdgcn_wave_barrier();
-      if (h == 0) ea_lds[wave][r] = ea;
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-#pragma unroll
-      for (int g = 0; g < 4; g++) {
-        const i32x4 e4 = *reinterpret_cast<const i32x4*>(&ea_lds[wave][8 * g + 4 * h]);
-#pragma unroll
-        for (int t = 0; t < 4; t++) {
-          const int x = 4 * g + t;
-          const int M = e4[t] + eb;
-          const int mn = max(em[x], M);
-          sm[x] = __builtin_ldexpf(sm[x], em[x] - mn) + __builtin_ldexpf(c[x], M - mn);
-          em[x] = mn;
-        }
-      }
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
+      join(c, ea, eb, 0);
     }
-  }
+  };
+  // register x of the tile: row 8 (x / 4) + 4 h + x % 4, column r; is it a cell of the band?
+  auto stored = [&](int x) {
+    const int ci = i0 + 8 * (x >> 2) + 4 * h + (x & 3), cj = j0 + r;
+    return ci < n && cj < n && cj - ci >= static_cast<int>(dlo) && cj - ci <= dtop;
+  };
+  // may the final pair of a stored cell have lost terms to underflow (header)?
+  auto doubtful = [&](int x, int mn, float s) { return stored(x) && s < kMxFloor && mn > kMxNone / 2; };
+  accumulate(false);
   auto finish = [&](int x, int mn, float s) {  // register x of the tile: row 8 (x / 4) + 4 h + x % 4, column r
     const int ci = i0 + 8 * (x >> 2) + 4 * h + (x & 3), cj = j0 + r;
     const int d = cj - ci;
@@ -232,29 +306,48 @@ k_tree_mid_mx(TreeBatch b, uint32_t dlo, uint32_t dhi, uint32_t thr, int outside
     }
   };
   if (KS == 1) {
+    bool bad = false;
+#pragma unroll
+    for (int x = 0; x < 16; x++) bad = bad || doubtful(x, em[x], sm[x]);
+    if (__builtin_amdgcn_ballot_w64(bad) != 0ull) accumulate(true);  // (uniform in the wave: the tile is its own)
 #pragma unroll
     for (int x = 0; x < 16; x++) finish(x, em[x], sm[x]);
     return;
   }
   // the four waves' partial sums meet: wave w finishes registers 4 w .. 4 w + 3 (rows 8 w + 4 h + t)
+  int mv[4];
+  float sv[4];
+  auto meet = [&]() {
 #pragma unroll
-  for (int x = 0; x < 16; x++) red[wave][x][lane] = make_float2(__int_as_float(em[x]), sm[x]);
-  __syncthreads();
+    for (int x = 0; x < 16; x++) red[wave][x][lane] = make_float2(__int_as_float(em[x]), sm[x]);
+    __syncthreads();
 #pragma unroll
-  for (int t = 0; t < 4; t++) {
-    const int x = 4 * static_cast<int>(wave) + t;
-    int mn = kMxNone;
-    float2 v[kMxWaves];
+    for (int t = 0; t < 4; t++) {
+      const int x = 4 * static_cast<int>(wave) + t;
+      int mn = kMxNone;
+      float2 v[kMxWaves];
 #pragma unroll
-    for (int w = 0; w < kMxWaves; w++) {
-      v[w] = red[w][x][lane];
-      mn = max(mn, __float_as_int(v[w].x));
+      for (int w = 0; w < kMxWaves; w++) {
+        v[w] = red[w][x][lane];
+        mn = max(mn, __float_as_int(v[w].x));
+      }
+      float s = 0.f;
+#pragma unroll
+      for (int w = 0; w < kMxWaves; w++) s += __builtin_ldexpf(v[w].y, __float_as_int(v[w].x) - mn);
+      mv[t] = mn;
+      sv[t] = s;
     }
-    float s = 0.f;
+  };
+  meet();
+  bool bad = false;
 #pragma unroll
-    for (int w = 0; w < kMxWaves; w++) s += __builtin_ldexpf(v[w].y, __float_as_int(v[w].x) - mn);
-    finish(x, mn, s);
+  for (int t = 0; t < 4; t++) bad = bad || doubtful(4 * static_cast<int>(wave) + t, mv[t], sv[t]);
+  if (__syncthreads_or(bad ? 1 : 0)) {  // (uniform in the workgroup; every read of `red` is behind this barrier)
+    accumulate(true);
+    meet();
   }
+#pragma unroll
+  for (int t = 0; t < 4; t++) finish(4 * static_cast<int>(wave) + t, mv[t], sv[t]);
 }
 
 }  // namespace
