@@ -65,6 +65,9 @@ extern "C" {
   fn rnamc_window_plan(n: u64, window: u32, stride: u32, max_bp_span: u32, n_windows: *mut u64, band: *mut u32, starts: *mut u64, starts_cap: u64) -> c_int;
   fn rnamc_bpp_windowed(ctx: *mut RnamcCtx, bases: *const u8, n: u64, constraint: *const c_char, window: u32, stride: u32, max_bp_span: u32, uses_contra_model: c_int, allows_short_hairpins: c_int, band_prob: *mut f32, paired_prob: *mut f32, window_log_partition: *mut f32) -> c_int;
   fn rnamc_bpp_windowed_multi(pool: *mut RnamcPool, bases: *const u8, n: u64, constraint: *const c_char, window: u32, stride: u32, max_bp_span: u32, uses_contra_model: c_int, allows_short_hairpins: c_int, band_prob: *mut f32, paired_prob: *mut f32, window_log_partition: *mut f32) -> c_int;
+  fn rnamc_mutant_plan(bases: *const u8, n: u32, positions: *const u32, n_positions: u32, n_mutants: *mut u64, mut_pos: *mut u32, mut_base: *mut u8, cap: u64) -> c_int;
+  fn rnamc_mutant_scan(ctx: *mut RnamcCtx, bases: *const u8, n: u32, constraint: *const c_char, max_bp_span: u32, uses_contra_model: c_int, allows_short_hairpins: c_int, positions: *const u32, n_positions: u32, log_partition: *mut f32, pair_dist2_q: *mut i64, max_dp: *mut f32, max_i: *mut u32, max_j: *mut u32, paired_prob: *mut f32, wt_log_partition: *mut f32, wt_paired_prob: *mut f32) -> c_int;
+  fn rnamc_mutant_scan_multi(pool: *mut RnamcPool, bases: *const u8, n: u32, constraint: *const c_char, max_bp_span: u32, uses_contra_model: c_int, allows_short_hairpins: c_int, positions: *const u32, n_positions: u32, log_partition: *mut f32, pair_dist2_q: *mut i64, max_dp: *mut f32, max_i: *mut u32, max_j: *mut u32, paired_prob: *mut f32, wt_log_partition: *mut f32, wt_paired_prob: *mut f32) -> c_int;
   fn rnamc_fold_scores(ctx: *mut RnamcCtx, bases: *const u8, n: u32, uses_contra_model: c_int, allows_short_hairpins: c_int, hairpin_scores: *mut f32, multibranch_close_scores: *mut f32, accessible_scores: *mut f32, twoloop_scores: *mut TwoloopScore, twoloop_cap: u64, twoloop_count: *mut u64) -> c_int;
   fn rnamc_fold_sums(ctx: *mut RnamcCtx, bases: *const u8, n: u32, uses_contra_model: c_int, allows_short_hairpins: c_int, sums_external: *mut f32, sums_rightmost_basepairs_external: *mut f32, sums_rightmost_basepairs_multibranch: *mut f32, sums_close: *mut f32, sums_accessible: *mut f32, sums_multibranch: *mut f32, sums_1ormore_basepairs: *mut f32) -> c_int;
   fn rnamc_sample_batch(ctx: *mut RnamcCtx, n_seqs: u32, bases: *const u8, offsets: *const u64, uses_contra_model: c_int, allows_short_hairpins: c_int, n_samples: u32, seed: u64, structs: *mut u8, log_weights: *mut f32, log_partition: *mut f32) -> c_int;
@@ -458,6 +461,93 @@ pub fn mccaskill_algo_windowed(
     );
   });
   (band, paired_prob, band_width as usize)
+}
+
+// Point-mutation scan of one sequence (rnamc_mutant_scan_multi; no counterpart in the reference
+// crate): every single-base mutant of `positions` (None: every base; three mutants per position,
+// base codes ascending without the wild type's) folded and its pair-probability matrix compared with
+// the wild type's on the device.  dist2_q is the squared Euclidean distance in units of 2^-44;
+// max_pair is (u32::MAX, u32::MAX) where no pair moved; paired_prob holds one row of seq.len() per mutant.
+pub struct MutantScan {
+  pub pos: Vec<u32>,
+  pub base: Vec<u8>,
+  pub log_partition: Vec<f32>,
+  pub wt_log_partition: f32,
+  pub dist2_q: Vec<i64>,
+  pub max_dp: Vec<f32>,
+  pub max_pair: Vec<(u32, u32)>,
+  pub paired_prob: Vec<f32>,
+  pub wt_paired_prob: Vec<f32>,
+}
+
+pub fn mutant_scan(
+  seq: SeqSlice,
+  uses_contra_model: bool,
+  allows_short_hairpins: bool,
+  fold_score_sets: &FoldScoreSets,
+  positions: Option<&[u32]>,
+  max_bp_span: u32,
+) -> MutantScan {
+  let bases: Vec<u8> = seq.iter().map(|&x| x as u8).collect();
+  let n = bases.len();
+  let (pos_ptr, n_pos) = match positions {
+    Some(p) => (p.as_ptr(), p.len() as u32),
+    None => (std::ptr::null(), 0u32),
+  };
+  let mut n_mutants = 0u64;
+  check(
+    unsafe { rnamc_mutant_plan(bases.as_ptr(), n as u32, pos_ptr, n_pos, &mut n_mutants, std::ptr::null_mut(), std::ptr::null_mut(), 0) },
+    "rnamc_mutant_plan",
+  );
+  let m = n_mutants as usize;
+  let (mut pos, mut base) = (vec![0u32; m.max(1)], vec![0u8; m.max(1)]);
+  check(
+    unsafe { rnamc_mutant_plan(bases.as_ptr(), n as u32, pos_ptr, n_pos, &mut n_mutants, pos.as_mut_ptr(), base.as_mut_ptr(), n_mutants) },
+    "rnamc_mutant_plan",
+  );
+  let mut log_partition = vec![0f32; m.max(1)];
+  let mut dist2_q = vec![0i64; m.max(1)];
+  let mut max_dp = vec![0f32; m.max(1)];
+  let (mut max_i, mut max_j) = (vec![0u32; m.max(1)], vec![0u32; m.max(1)]);
+  let mut paired_prob = vec![0f32; (m * n).max(1)];
+  let mut wt_log_partition = 0f32;
+  let mut wt_paired_prob = vec![0f32; n];
+  with_pool(fold_score_sets, |pool| {
+    check(
+      unsafe {
+        rnamc_mutant_scan_multi(
+          pool,
+          bases.as_ptr(),
+          n as u32,
+          std::ptr::null(),
+          max_bp_span,
+          uses_contra_model as c_int,
+          allows_short_hairpins as c_int,
+          pos_ptr,
+          n_pos,
+          log_partition.as_mut_ptr(),
+          dist2_q.as_mut_ptr(),
+          max_dp.as_mut_ptr(),
+          max_i.as_mut_ptr(),
+          max_j.as_mut_ptr(),
+          paired_prob.as_mut_ptr(),
+          &mut wt_log_partition,
+          wt_paired_prob.as_mut_ptr(),
+        )
+      },
+      "rnamc_mutant_scan_multi",
+    );
+  });
+  for v in [&mut pos, &mut max_i, &mut max_j] {
+    v.truncate(m);
+  }
+  base.truncate(m);
+  log_partition.truncate(m);
+  dist2_q.truncate(m);
+  max_dp.truncate(m);
+  paired_prob.truncate(m * n);
+  let max_pair = max_i.iter().zip(max_j.iter()).map(|(&i, &j)| (i, j)).collect();
+  MutantScan { pos, base, log_partition, wt_log_partition, dist2_q, max_dp, max_pair, paired_prob, wt_paired_prob }
 }
 
 pub fn mccaskill_algo<T>(

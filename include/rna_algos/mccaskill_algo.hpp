@@ -311,6 +311,46 @@ inline WindowedBpp mccaskill_algo_windowed(const Context& ctx, const Seq& seq, u
 }
 // the same over a pool's devices: rnamc_bpp_windowed_multi (same arguments, a rnamc_pool* first)
 
+// Point-mutation scan of one sequence (rnamc_mutant_scan; no counterpart in the reference): every
+// single-base mutant of `positions` (empty: every base; three mutants per position, base codes ascending
+// without the wild type's) folded and its pair-probability matrix compared with the wild type's on the
+// device.  dist2_q is the squared Euclidean distance in units of 2^-44, max_i = max_j = 0xffffffff where
+// no pair moved, paired_prob holds one row of seq.size() per mutant.
+struct MutantScan {
+  std::vector<uint32_t> pos, max_i, max_j;
+  std::vector<uint8_t> base;
+  std::vector<float> log_partition, max_dp, paired_prob, wt_paired_prob;
+  std::vector<int64_t> dist2_q;
+  float wt_log_partition = 0.f;
+  double dist2(size_t m) const { return static_cast<double>(dist2_q[m]) / 17592186044416.0; }  // 2^44
+};
+inline MutantScan mutant_scan(const Context& ctx, const Seq& seq, bool uses_contra_model, bool allows_short_hairpins,
+                              const std::vector<uint32_t>& positions = {}, uint32_t max_bp_span = 0,
+                              const char* constraint = nullptr) {
+  MutantScan r;
+  const uint32_t n = static_cast<uint32_t>(seq.size());
+  const uint32_t* pos = positions.empty() ? nullptr : positions.data();
+  const uint32_t n_pos = static_cast<uint32_t>(positions.size());
+  uint64_t m = 0;
+  check(rnamc_mutant_plan(seq.data(), n, pos, n_pos, &m, nullptr, nullptr, 0));
+  r.pos.resize(m);
+  r.base.resize(m);
+  check(rnamc_mutant_plan(seq.data(), n, pos, n_pos, &m, r.pos.data(), r.base.data(), m));
+  r.log_partition.resize(m ? m : 1);
+  r.dist2_q.resize(m);
+  r.max_dp.resize(m);
+  r.max_i.resize(m);
+  r.max_j.resize(m);
+  r.paired_prob.resize(m * n);
+  r.wt_paired_prob.resize(n);
+  check(rnamc_mutant_scan(ctx.get(), seq.data(), n, constraint, max_bp_span, uses_contra_model, allows_short_hairpins,
+                          pos, n_pos, r.log_partition.data(), r.dist2_q.data(), r.max_dp.data(), r.max_i.data(),
+                          r.max_j.data(), r.paired_prob.data(), &r.wt_log_partition, r.wt_paired_prob.data()));
+  r.log_partition.resize(m);
+  return r;
+}
+// the same over a pool's devices: rnamc_mutant_scan_multi (same arguments, a rnamc_pool* first)
+
 // Boltzmann sampling (rnamc_sample_batch; no counterpart in the reference): n_samples structures
 // per sequence, each drawn with probability exp(log_weight) / exp(log_partition).  Sample t of
 // sequence s is a pure function of (tables, sequence, flags, seed, s, t).

@@ -42,7 +42,7 @@ extern "C" {
  *    rnamc_sample_batch_constrained, rnamc_mfe_batch_constrained, rnamc_log_partition_batch,
  *    rnamc_constraint_check, rnamc_centroid_fold_batch, rnamc_centroid_fold_batch_multi,
  *    rnamc_bpp_batch_sparse, rnamc_bpp_batch_sparse_multi, rnamc_window_plan, rnamc_bpp_windowed,
- *    rnamc_bpp_windowed_multi */
+ *    rnamc_bpp_windowed_multi, rnamc_mutant_plan, rnamc_mutant_scan, rnamc_mutant_scan_multi */
 #define RNAMC_ABI_VERSION 3u
 
 /* Compile-time limits.  In the reference these are constants of rna-ss-params
@@ -366,6 +366,11 @@ typedef struct rnamc_batch_stats {
    * is on, their summed device time */
   uint64_t launches_window;
   double ms_window;
+  /* rnamc_mutant_scan: the statistics above summed over the wild-type fold and the call's chunks, and
+   * the launches of its own kernels (compare, paired; also counted in launches_other) with, when
+   * profiling is on, their summed device time */
+  uint64_t launches_mutant;
+  double ms_mutant;
 } rnamc_batch_stats;
 int rnamc_ctx_last_stats(rnamc_ctx* ctx, rnamc_batch_stats* out);
 /* The same with the caller's idea of the struct size: copies min(out_bytes, sizeof) bytes, so a
@@ -738,6 +743,78 @@ int rnamc_bpp_windowed_multi(rnamc_pool* pool, const uint8_t* bases, uint64_t n,
                              uint32_t window, uint32_t stride, uint32_t max_bp_span,
                              int uses_contra_model, int allows_short_hairpins, float* band_prob,
                              float* paired_prob, float* window_log_partition);
+
+/* ------------------------------------------------------------------------- */
+/* Point-mutation scan of ONE sequence (the riboSNitch / SNPfold / RNAsnp / RNAmute question): every
+ * single-base mutant of the listed positions is folded and its pair-probability matrix compared
+ * with the wild type's on the device.  No triangle reaches the host.
+ *   bases, n      the wild type, base codes 0..3, 1 <= n <= 65535
+ *   constraint    NULL or the wild type's n bytes over ". x ( ) < >": every record of the call has
+ *                 the same length, so brackets are legal; each mutant is folded under the same string
+ *   max_bp_span, flags   as rnamc_bpp_batch_constrained
+ *   positions     NULL: every base 0 .. n-1 (n_positions is then ignored).  Otherwise n_positions
+ *                 entries, each < n, taken as given: any order, duplicates legal (each gives its three
+ *                 mutants again).
+ * Mutant list: the idx-th listed position x contributes three mutants, base codes b in
+ * {0,1,2,3} \ {bases[x]} ascending.  Mutant m = 3 * idx + rank, M = 3 * (number of positions).
+ * Folds: the wild type as a call of one record; the mutants in chunks of records (knob
+ * "mutant_chunk_nt", rnamc_ctx_set: nucleotides of mutants that go through one staged call of the
+ * sweep, default 64 Mi, never less than one mutant).  Every fold runs exactly as
+ * rnamc_bpp_batch_constrained folds those records with the same constraint and max_bp_span, in the
+ * context's summation mode.  In mode 0 nothing depends on chunking, grouping, knobs or the number of
+ * devices; in mode 1 the sweep picks its form per staged call ("tree_lane_min_nt"), as it does for
+ * rnamc_bpp_batch_constrained on the same records: there the chunk is part of the input.
+ * Per mutant m, against the wild type's triangle.  Both are diagonal-major packed triangles of the
+ * same n: packed cell c of one is cell c of the other (rnamc_bpp_index).  Cells of span 0 (c < n)
+ * are skipped.  wt[c] / mut[c]: the f32 cells, absent pairs at -1.
+ *   log_partition[m]   ln Z of the mutant (never NULL)
+ *   pair_dist2_q[m]    the squared Euclidean distance of the two pair-probability matrices in fixed
+ *                 point, exact and order-free.  Per cell a = wt[c] > -0.5 ? (double)wt[c] : 0.0, b
+ *                 likewise from mut[c]; e = a - b (one f64 subtraction);
+ *                 q = min(rint(e * e * 2^44), 2^45): one correctly rounded f64 multiply e * e, fused
+ *                 with nothing, an exact scaling by 2^44, rint to nearest with ties to even.  The
+ *                 output is the signed 64-bit sum of q over the cells; the distance is
+ *                 pair_dist2_q / 2^44.  No overflow: (a - b)^2 <= a + b for a, b in [0, 1], and each
+ *                 base's pair probabilities sum to at most about 1, so the sum over the cells of
+ *                 (a - b)^2 <= sum a + sum b <= n <= 65535 < 2^16: the integer sum stays below
+ *                 2^61 (and a cell that rounding pushed above 1 is capped at 2^45).
+ *   max_dp[m], max_i[m], max_j[m]   the pair that moved most.  Per cell t = |fa - fb| with
+ *                 fa = wt[c] > -0.5 ? wt[c] : 0.0f, fb likewise (one f32 subtraction).  Only cells
+ *                 with t > 0 take part; the largest t wins, ties go to the smallest packed index c;
+ *                 (max_i, max_j) is that cell's pair, i < j.  No cell takes part: max_dp = 0 and
+ *                 max_i = max_j = 0xffffffff.
+ *   paired_prob   M rows of n f32 (may be NULL): row m is the mutant's per-base paired probability
+ *                 as rnamc_bpp_batch_sparse defines paired_prob, in its summation order, bit for bit
+ *   wt_log_partition   one f32, wt_paired_prob   n f32: the same two quantities of the wild type
+ * Every output pointer except log_partition may be NULL.
+ * Errors, all before any device work: RNAMC_ERR_INVALID_ARG for a NULL ctx / pool / bases /
+ * log_partition, a position >= n, 3 * n_positions >= 2^32, a bad constraint (its position in
+ * rnamc_last_error()); RNAMC_ERR_EMPTY_SEQ, RNAMC_ERR_SEQ_TOO_LONG, RNAMC_ERR_INVALID_BASE as
+ * elsewhere.  n_positions == 0 with a non-NULL list writes only the wild-type outputs and returns
+ * RNAMC_OK.  RNAMC_ERR_OOM when the wild type's triangle (n(n+1)/2 floats, kept for the whole call)
+ * or the per-mutant buffers (16 bytes per mutant, and n floats per mutant of a chunk with
+ * paired_prob) do not fit the device. */
+
+/* Host only, no device: the mutant list of a call.  *n_mutants (never NULL) is always set to M;
+ * mut_pos and mut_base (each may be NULL) receive position and base code of every mutant,
+ * RNAMC_ERR_INVALID_ARG when one is given and cap < M (the count still set, nothing written).  The
+ * argument checks of rnamc_mutant_scan on bases, n, positions and n_positions apply. */
+int rnamc_mutant_plan(const uint8_t* bases, uint32_t n, const uint32_t* positions, uint32_t n_positions,
+                      uint64_t* n_mutants, uint32_t* mut_pos, uint8_t* mut_base, uint64_t cap);
+int rnamc_mutant_scan(rnamc_ctx* ctx, const uint8_t* bases, uint32_t n, const char* constraint,
+                      uint32_t max_bp_span, int uses_contra_model, int allows_short_hairpins,
+                      const uint32_t* positions, uint32_t n_positions, float* log_partition,
+                      int64_t* pair_dist2_q, float* max_dp, uint32_t* max_i, uint32_t* max_j,
+                      float* paired_prob, float* wt_log_partition, float* wt_paired_prob);
+/* The same over the pool's devices: the mutant list is cut into contiguous shards
+ * (rnamc_shard_plan: equal records, equal bands); every context folds the wild type itself and
+ * scans its shard straight into the caller's arrays.  Nothing is summed across devices:
+ * bit-identical to the single-context entry in summation mode 0. */
+int rnamc_mutant_scan_multi(rnamc_pool* pool, const uint8_t* bases, uint32_t n, const char* constraint,
+                            uint32_t max_bp_span, int uses_contra_model, int allows_short_hairpins,
+                            const uint32_t* positions, uint32_t n_positions, float* log_partition,
+                            int64_t* pair_dist2_q, float* max_dp, uint32_t* max_i, uint32_t* max_j,
+                            float* paired_prob, float* wt_log_partition, float* wt_paired_prob);
 
 #ifdef __cplusplus
 }

@@ -35,6 +35,7 @@ SYMBOLS = [
     "rnamc_constraint_check", "rnamc_centroid_fold_batch", "rnamc_centroid_fold_batch_multi",
     "rnamc_bpp_batch_sparse", "rnamc_bpp_batch_sparse_multi",
     "rnamc_window_plan", "rnamc_bpp_windowed", "rnamc_bpp_windowed_multi",
+    "rnamc_mutant_plan", "rnamc_mutant_scan", "rnamc_mutant_scan_multi",
 ]
 
 
@@ -58,6 +59,7 @@ class BatchStats(C.Structure):
         ("ms_outside_main", C.c_double), ("ms_outside_tail", C.c_double),
         ("ms_outside_small", C.c_double), ("tree_side_stream", C.c_uint64),
         ("launches_window", C.c_uint64), ("ms_window", C.c_double),
+        ("launches_mutant", C.c_uint64), ("ms_mutant", C.c_double),
     ]
 
 
@@ -186,6 +188,13 @@ def lib():
     L.rnamc_bpp_windowed.argtypes = [vp, vp, C.c_uint64, C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int,
                                      C.c_int, vp, vp, vp]
     L.rnamc_bpp_windowed_multi.argtypes = L.rnamc_bpp_windowed.argtypes
+    # (bases, n, positions, n_positions, n_mutants, mut_pos, mut_base, cap)
+    L.rnamc_mutant_plan.argtypes = [vp, C.c_uint32, vp, C.c_uint32, u64p, vp, vp, C.c_uint64]
+    # (ctx or pool, bases, n, constraint, max_bp_span, contra, short hairpins, positions, n_positions,
+    # log_partition, pair_dist2_q, max_dp, max_i, max_j, paired_prob, wt_log_partition, wt_paired_prob)
+    L.rnamc_mutant_scan.argtypes = [vp, vp, C.c_uint32, C.c_char_p, C.c_uint32, C.c_int, C.c_int, vp, C.c_uint32,
+                                    vp, vp, vp, vp, vp, vp, vp, vp]
+    L.rnamc_mutant_scan_multi.argtypes = L.rnamc_mutant_scan.argtypes
     _lib = L
     return L
 

@@ -177,6 +177,14 @@ void rnamc_ctx_destroy(rnamc_ctx* c) {
     if (c->wn_band) (void)hipFree(c->wn_band);
     if (c->wn_paired) (void)hipFree(c->wn_paired);
     for (hipEvent_t e : c->wn_events) (void)hipEventDestroy(e);
+    if (c->mt_wt) (void)hipFree(c->mt_wt);
+    if (c->mt_wt_paired) (void)hipFree(c->mt_wt_paired);
+    if (c->mt_items) (void)hipFree(c->mt_items);
+    if (c->mt_pitems) (void)hipFree(c->mt_pitems);
+    if (c->mt_sum) (void)hipFree(c->mt_sum);
+    if (c->mt_key) (void)hipFree(c->mt_key);
+    if (c->mt_paired) (void)hipFree(c->mt_paired);
+    for (hipEvent_t e : c->mt_events) (void)hipEventDestroy(e);
   }
   delete c;
 }
@@ -254,6 +262,8 @@ int rnamc_ctx_set(rnamc_ctx* c, const char* name, int64_t value) {
     c->centroid_chunk_bytes = value;
   } else if (k == "window_chunk_nt" && value >= 1) {
     c->window_chunk_nt = value;
+  } else if (k == "mutant_chunk_nt" && value >= 1) {
+    c->mutant_chunk_nt = value;
   } else if (k == "block_threads" && value >= 64 && value <= 256 && value % 64 == 0) {
     // (the sweep kernels are compiled with __launch_bounds__(256))
     c->block_threads = value;

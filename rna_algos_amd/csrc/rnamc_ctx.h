@@ -202,6 +202,22 @@ struct rnamc_ctx {
   uint64_t wn_items_cap = 0, wn_sum_cap = 0, wn_cnt_cap = 0, wn_band_cap = 0, wn_paired_cap = 0;
   std::vector<hipEvent_t> wn_events;  // profiling: a pair around every run of window kernels
   int64_t window_chunk_nt = 64ll << 20;
+  // rnamc_mutant_scan (grow-only): the wild type's triangle and paired probabilities, kept for the
+  // whole call; a chunk's descriptors for the compare and the paired kernel; the call's accumulators
+  // (one sum and one max key per mutant) and a chunk's paired probabilities ([record * n + x]).
+  // mutant_chunk_nt: nucleotides of mutants that go through one staged call of the sweep (never
+  // less than one mutant)
+  float* mt_wt = nullptr;
+  float* mt_wt_paired = nullptr;
+  rnamc::MutantItem* mt_items = nullptr;
+  rnamc::SparseItem* mt_pitems = nullptr;
+  int64_t* mt_sum = nullptr;
+  uint64_t* mt_key = nullptr;
+  float* mt_paired = nullptr;
+  uint64_t mt_wt_cap = 0, mt_wt_paired_cap = 0, mt_items_cap = 0, mt_pitems_cap = 0, mt_sum_cap = 0, mt_key_cap = 0,
+           mt_paired_cap = 0;
+  std::vector<hipEvent_t> mt_events;  // profiling: a pair around every run of mutant kernels
+  int64_t mutant_chunk_nt = 64ll << 20;
 };
 
 namespace rnamc {

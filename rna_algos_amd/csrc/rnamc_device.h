@@ -192,6 +192,26 @@ void launch_window_finalize(const WindowGeom& g, const int64_t* sum, const uint3
 void launch_window_paired(const WindowGeom& g, const int64_t* sum, const uint32_t* cnt, float* paired,
                           hipStream_t st);
 
+// point-mutation scan (rnamc_mutant.hip): the triangles of a group of mutants, all
+// of length n, against the wild type's resident triangle
+struct MutantItem {
+  uint64_t bpp_off;  // float offset of the mutant's bpp triangle in `bpp`
+  uint64_t slot;     // its entry in the call's accumulators
+};
+// Cells of a strip (one workgroup each) for triangles of `len` cells: 4096 while at most 64 of them
+// cover the triangle, beyond that a 64th of it rounded up to whole workgroup steps of 256 cells -- a
+// mutant takes at most 64 atomics of either kind however long it is.
+constexpr uint32_t kMutantMinStrip = 4096u, kMutantMaxStrips = 64u;
+inline uint32_t mutant_strip_of(uint64_t len) {
+  const uint64_t per = (len + kMutantMaxStrips - 1u) / kMutantMaxStrips;
+  const uint64_t strip = (per + 255u) / 256u * 256u;
+  return static_cast<uint32_t>(strip < kMutantMinStrip ? kMutantMinStrip : strip);
+}
+// at most 65535 items a launch; sum[slot] += the fixed-point squared distance of item and wild type,
+// key[slot] = max(key[slot], (bits(|dp|) << 32) | (0xffffffff - cell)) over the cells that moved
+void launch_mutant_compare(const MutantItem* items, uint32_t n_items, const float* wt, const float* bpp, uint32_t n,
+                           int64_t* sum, uint64_t* key, hipStream_t st);
+
 // ---- tree-order summation mode (rnamc_tree.hip) ----
 // Dense n x n matrices with row stride ld (>= n + 32, a multiple of 32 floats), msz floats
 // each; "row" = [i * ld + j], "col" = [j * ld + i].  The outside sweep reuses four slots.

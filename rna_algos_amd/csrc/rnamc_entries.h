@@ -138,6 +138,45 @@ inline int group_triangles(rnamc_ctx* c, size_t g, float** out_base) {
   return RNAMC_OK;
 }
 
+// Entries that run the sweep several times in one call (chunks of windows, of mutants): the sweep's
+// statistics of one staged call added to the call's (run_batch* resets the context's when it starts)
+inline void add_sweep_stats(rnamc_batch_stats* to, const rnamc_batch_stats& s) {
+  to->n_groups += s.n_groups;
+  to->launches_inside += s.launches_inside;
+  to->launches_outside += s.launches_outside;
+  to->launches_other += s.launches_other;
+  to->ms_inside += s.ms_inside;
+  to->ms_outside += s.ms_outside;
+  to->ms_other += s.ms_other;
+  to->workspace_bytes = std::max(to->workspace_bytes, s.workspace_bytes);
+  to->launches_outside_main += s.launches_outside_main;
+  to->launches_outside_tail += s.launches_outside_tail;
+  to->launches_outside_small += s.launches_outside_small;
+  to->ms_outside_main += s.ms_outside_main;
+  to->ms_outside_tail += s.ms_outside_tail;
+  to->ms_outside_small += s.ms_outside_small;
+  to->tree_side_stream = s.tree_side_stream;
+}
+
+// profiling: event pairs around an entry's own kernels (pair p = events 2p, 2p + 1 of a grow-only
+// ring of the context), read once their stream is drained
+inline int event_pairs(std::vector<hipEvent_t>* ring, size_t pairs) {
+  while (ring->size() < 2 * pairs) {
+    hipEvent_t e;
+    HIPCHK(hipEventCreate(&e));
+    ring->push_back(e);
+  }
+  return RNAMC_OK;
+}
+inline int event_pairs_ms(const std::vector<hipEvent_t>& ring, size_t pairs, double* ms) {
+  for (size_t p = 0; p < pairs; p++) {
+    float t = 0.f;
+    HIPCHK(hipEventElapsedTime(&t, ring[2 * p], ring[2 * p + 1]));
+    *ms += t;
+  }
+  return RNAMC_OK;
+}
+
 // Waves of a walk kernel (sampling, tracebacks), one item each while they last: enough to fill the
 // chip, no more than the items, within 1 GB of stacks (the longest n + 1 pending cells per wave).
 inline uint32_t waves_of(int cus, uint64_t items, uint32_t gmax) {

@@ -62,43 +62,6 @@ WindowGeom geom_of(const WindowPlan& wp) {
   return g;
 }
 
-// profiling: event pairs around the window kernels, read once their stream is drained
-int window_events(rnamc_ctx* c, size_t pairs) {
-  while (c->wn_events.size() < 2 * pairs) {
-    hipEvent_t e;
-    HIPCHK(hipEventCreate(&e));
-    c->wn_events.push_back(e);
-  }
-  return RNAMC_OK;
-}
-
-int window_events_ms(rnamc_ctx* c, size_t pairs, double* ms) {
-  for (size_t p = 0; p < pairs; p++) {
-    float t = 0.f;
-    HIPCHK(hipEventElapsedTime(&t, c->wn_events[2 * p], c->wn_events[2 * p + 1]));
-    *ms += t;
-  }
-  return RNAMC_OK;
-}
-
-void add_stats(rnamc_batch_stats* to, const rnamc_batch_stats& s) {
-  to->n_groups += s.n_groups;
-  to->launches_inside += s.launches_inside;
-  to->launches_outside += s.launches_outside;
-  to->launches_other += s.launches_other;
-  to->ms_inside += s.ms_inside;
-  to->ms_outside += s.ms_outside;
-  to->ms_other += s.ms_other;
-  to->workspace_bytes = std::max(to->workspace_bytes, s.workspace_bytes);
-  to->launches_outside_main += s.launches_outside_main;
-  to->launches_outside_tail += s.launches_outside_tail;
-  to->launches_outside_small += s.launches_outside_small;
-  to->ms_outside_main += s.ms_outside_main;
-  to->ms_outside_tail += s.ms_outside_tail;
-  to->ms_outside_small += s.ms_outside_small;
-  to->tree_side_stream = s.tree_side_stream;
-}
-
 }  // namespace
 
 int bpp_windowed_accumulate(rnamc_ctx* c, const WindowPlan& wp, const uint8_t* bases, const char* constraint,
@@ -167,7 +130,7 @@ int bpp_windowed_accumulate(rnamc_ctx* c, const WindowPlan& wp, const uint8_t* b
         HIPCHK(hipMemcpyAsync(c->wn_items, items.data(), static_cast<uint64_t>(m) * sizeof(WindowItem),
                               hipMemcpyHostToDevice, st));
         if (prof)
-          if (int rc = window_events(c, c->group_begin.size() - 1)) return rc;
+          if (int rc = event_pairs(&c->wn_events, c->group_begin.size() - 1)) return rc;
       }
       return group_triangles(c, g, out_base);
     };
@@ -194,8 +157,8 @@ int bpp_windowed_accumulate(rnamc_ctx* c, const WindowPlan& wp, const uint8_t* b
     rc = sc.finish(c, rc, m, window_log_partition ? window_log_partition + first + x0 : nullptr);
     if (rc) return rc;
     if (prof)
-      if (int rc2 = window_events_ms(c, ev_pairs, &c->stats.ms_window)) return rc2;
-    add_stats(&total, c->stats);
+      if (int rc2 = event_pairs_ms(c->wn_events, ev_pairs, &c->stats.ms_window)) return rc2;
+    add_sweep_stats(&total, c->stats);
     total.launches_window += c->stats.launches_window;
     total.ms_window += c->stats.ms_window;
   }
@@ -227,7 +190,7 @@ int bpp_windowed_finish(rnamc_ctx* c, const WindowPlan& wp, const int64_t* sum, 
     HIPCHK(grow_device(reinterpret_cast<void**>(&c->wn_paired), &c->wn_paired_cap, wp.n * sizeof(float)));
   const bool prof = c->profile != 0;
   if (prof) {
-    if (int rc = window_events(c, 1)) return rc;
+    if (int rc = event_pairs(&c->wn_events, 1)) return rc;
     HIPCHK(hipEventRecord(c->wn_events[0], st));
   }
   const WindowGeom g = geom_of(wp);
@@ -246,7 +209,7 @@ int bpp_windowed_finish(rnamc_ctx* c, const WindowPlan& wp, const int64_t* sum, 
   c->stats.launches_other += launches;
   c->stats.launches_window += launches;
   if (prof)
-    if (int rc = window_events_ms(c, 1, &c->stats.ms_window)) return rc;
+    if (int rc = event_pairs_ms(c->wn_events, 1, &c->stats.ms_window)) return rc;
   return RNAMC_OK;
 }
 

@@ -77,6 +77,21 @@ int bpp_windowed_fetch(rnamc_ctx* c, const WindowPlan& wp, int64_t* sum, uint32_
 int bpp_windowed_finish(rnamc_ctx* c, const WindowPlan& wp, const int64_t* sum, const uint32_t* cnt,
                         float* band_prob, float* paired_prob);
 
+// rnamc_mutant_scan behind its two entries (rnamc_entries_mutant.cpp).
+// base code of the rank-th (0 .. 2) mutant of a position whose wild-type base is wt: {0,1,2,3} \ {wt} ascending
+inline uint8_t mutant_base_of(uint8_t wt, uint32_t rank) { return static_cast<uint8_t>(rank + (rank >= wt ? 1u : 0u)); }
+// every check of the entry that needs no context: pointers, the record, the position list, the
+// constraint; *n_mutants = 3 * (number of positions)
+int mutant_scan_check(const uint8_t* bases, uint32_t n, const char* constraint, const uint32_t* positions,
+                      uint32_t n_positions, const float* log_partition, uint64_t* n_mutants);
+// Runs with c->mu HELD by the caller and the context's device current: folds the wild type, then
+// mutants [first, first + count) of the list chunk by chunk.  The per-mutant outputs are the call's
+// whole arrays (indexed by m); the wild-type outputs may be NULL (a pool's later shards).
+int mutant_scan_core(rnamc_ctx* c, const uint8_t* bases, uint32_t n, const char* constraint, uint32_t max_bp_span,
+                     int uses_contra_model, int allows_short_hairpins, const uint32_t* positions, uint64_t first,
+                     uint64_t count, float* log_partition, int64_t* pair_dist2_q, float* max_dp, uint32_t* max_i,
+                     uint32_t* max_j, float* paired_prob, float* wt_log_partition, float* wt_paired_prob);
+
 // DP matrices of one sequence inside the workspace.  Every matrix is a packed
 // upper triangle of n(n+1)/2 f32 (padded to a multiple of 64 floats):
 //  - "diag-major": cell (i,j) at  d*n - d(d-1)/2 + i  with d = j-i.  A lane that

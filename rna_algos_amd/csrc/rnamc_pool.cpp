@@ -543,4 +543,79 @@ int rnamc_bpp_windowed_multi(rnamc_pool* p, const uint8_t* bases, uint64_t n, co
                                     n_shards > 1 ? shards[0].cnt.data() : nullptr, band_prob, paired_prob);
 }
 
+// rnamc_mutant_scan over the pool: the mutant list cut into shards (equal records: contiguous bands of
+// equal size); every context folds the wild type itself and scans its shard straight into the caller's
+// arrays.  Per-mutant integers, nothing summed across devices: the bits of the single-context entry.
+int rnamc_mutant_scan_multi(rnamc_pool* p, const uint8_t* bases, uint32_t n, const char* constraint,
+                            uint32_t max_bp_span, int uses_contra_model, int allows_short_hairpins,
+                            const uint32_t* positions, uint32_t n_positions, float* log_partition,
+                            int64_t* pair_dist2_q, float* max_dp, uint32_t* max_i, uint32_t* max_j,
+                            float* paired_prob, float* wt_log_partition, float* wt_paired_prob) {
+  if (!p) return RNAMC_ERR_INVALID_ARG;
+  uint64_t total = 0;
+  if (int rc = rnamc::mutant_scan_check(bases, n, constraint, positions, n_positions, log_partition, &total))
+    return rc;
+  if (p->ctxs.empty()) return RNAMC_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> lock(p->mu);
+  const uint32_t nm = static_cast<uint32_t>(total);  // (below 2^32: checked)
+  const uint32_t n_shards = static_cast<uint32_t>(std::min<uint64_t>(p->ctxs.size(), std::max(nm, 1u)));
+  struct Shard {
+    uint64_t first = 0, count = 0;
+    int status = RNAMC_OK;
+    std::string error;
+  };
+  std::vector<Shard> shards(n_shards);
+  try {  // nothing may throw across the C boundary
+    // the plan of rnamc_shard_plan over the mutants as records of n bases (the list's order is kept)
+    std::vector<uint64_t> offs(static_cast<size_t>(nm) + 1);
+    for (uint64_t x = 0; x <= nm; x++) offs[x] = x * n;
+    std::vector<uint32_t> shard_of(nm);
+    if (nm) plan(nm, offs.data(), n_shards, shard_of.data(), nullptr);
+    for (uint32_t x = 0; x < nm; x++) {
+      Shard& sh = shards[shard_of[x]];
+      if (sh.count == 0) sh.first = x;
+      sh.count++;
+    }
+  } catch (const std::exception&) {
+    rnamc::set_last_error("rnamc_mutant_scan_multi: no host memory");
+    return RNAMC_ERR_OOM;
+  }
+  auto work = [&](uint32_t k) {
+    Shard& sh = shards[k];
+    if (k != 0 && sh.count == 0) return;
+    rnamc_ctx* c = p->ctxs[k];
+    std::unique_lock<std::mutex> ctx_lock(c->mu);
+    rnamc::DeviceGuard guard(c->device);
+    if (!guard.ok) {
+      sh.status = RNAMC_ERR_NO_DEVICE;
+      return;
+    }
+    // (the wild type's outputs come from the first shard alone: every context computes the same bits)
+    sh.status = rnamc::mutant_scan_core(c, bases, n, constraint, max_bp_span, uses_contra_model,
+                                        allows_short_hairpins, positions, sh.first, sh.count, log_partition,
+                                        pair_dist2_q, max_dp, max_i, max_j, paired_prob,
+                                        k == 0 ? wt_log_partition : nullptr, k == 0 ? wt_paired_prob : nullptr);
+    if (sh.status) {
+      sh.error = rnamc_last_error();  // (thread-local: carry it to the caller's thread)
+      (void)hipStreamSynchronize(c->own_stream);
+    }
+  };
+  std::vector<std::thread> pool;
+  for (uint32_t k = 1; k < n_shards; k++) {
+    try {
+      pool.emplace_back(work, k);
+    } catch (...) {  // no thread: this shard runs on the caller's thread below
+      work(k);
+    }
+  }
+  work(0);
+  for (std::thread& t : pool) t.join();
+  for (const Shard& sh : shards)
+    if (sh.status) {
+      rnamc::set_last_error(sh.error);
+      return sh.status;
+    }
+  return RNAMC_OK;
+}
+
 }  // extern "C"

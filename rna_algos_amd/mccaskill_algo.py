@@ -271,6 +271,108 @@ def _bpp_windowed(entry, handle, seq, window, uses_contra_model, allows_short_ha
     return WindowedBpp(out, paired, logz, starts)
 
 
+class MutantScan:
+    """Result of a point-mutation scan (rnamc_mutant_scan), one entry per mutant m = 3 * idx + rank:
+    `pos` (u32) and `base` (u8 code) of the mutant, `log_z` (f32) and `wt_log_z` (float),
+    `dist2_q` (int64: the squared Euclidean distance of the mutant's pair-probability matrix from the
+    wild type's in units of 2^-44), `max_dp` (f32) with `max_pair` (M x 2 int64, -1 -1 where no pair
+    moved), `paired_prob` (M x n f32) and `wt_paired_prob` (f32[n])."""
+    DIST2_QUANTUM = float(2 ** 44)
+
+    def __init__(self, pos, base, log_z, wt_log_z, dist2_q, max_dp, max_pair, paired_prob, wt_paired_prob):
+        self.pos, self.base = pos, base
+        self.log_z, self.wt_log_z = log_z, float(wt_log_z)
+        self.dist2_q = dist2_q
+        self.max_dp, self.max_pair = max_dp, max_pair
+        self.paired_prob, self.wt_paired_prob = paired_prob, wt_paired_prob
+
+    def __len__(self):
+        return len(self.pos)
+
+    @property
+    def dist2(self):
+        """float64: dist2_q / 2^44"""
+        return self.dist2_q.astype(np.float64) / MutantScan.DIST2_QUANTUM
+
+    @property
+    def delta_log_z(self):
+        """float64: ln Z of the mutant - ln Z of the wild type"""
+        return self.log_z.astype(np.float64) - np.float64(self.wt_log_z)
+
+    def profile_correlation(self):
+        """SNPfold's score: Pearson r of every mutant's paired-probability profile with the wild
+        type's, in float64; NaN where either profile is constant."""
+        a = np.asarray(self.wt_paired_prob, dtype=np.float64)
+        b = np.asarray(self.paired_prob, dtype=np.float64).reshape(len(self), len(a))
+        da = a - a.mean() if len(a) else a
+        db = b - b.mean(axis=1, keepdims=True) if len(a) else b
+        den = np.sqrt(np.sum(da * da) * np.sum(db * db, axis=1))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.where(den > 0, np.sum(db * da[None, :], axis=1) / den, np.nan)
+
+    def top(self, k):
+        """indices of the k mutants with the largest dist2, descending (ties: the earlier mutant)"""
+        order = np.argsort(-self.dist2_q, kind="stable")
+        return order[:max(int(k), 0)]
+
+
+def _positions(positions):
+    """None or a u32 array of positions (RnamcError for one outside u32)"""
+    if positions is None:
+        return None
+    pos = np.asarray(positions, dtype=np.int64).reshape(-1)
+    if pos.size and (pos.min() < 0 or pos.max() >= 2 ** 32):
+        raise _lib.RnamcError(_lib.ERR_INVALID_ARG, "mutant positions must lie in 0 .. 2^32 - 1")
+    if 3 * pos.size >= 2 ** 32:
+        raise _lib.RnamcError(_lib.ERR_INVALID_ARG, "3 * n_positions must be below 2^32")
+    return np.ascontiguousarray(pos.astype(np.uint32))
+
+
+def mutant_plan(seq, positions=None):
+    """rnamc_mutant_plan (host only, no device): the mutant list of a scan -> (pos u32[M], base u8[M])"""
+    seq = np.ascontiguousarray(seq, dtype=np.uint8)
+    if seq.shape[0] > MAX_SEQ_LEN:
+        raise _lib.RnamcError(_lib.ERR_SEQ_TOO_LONG)
+    pos = _positions(positions)
+    head = (seq.ctypes.data, int(seq.shape[0]), None if pos is None else pos.ctypes.data,
+            0 if pos is None else len(pos))
+    count = C.c_uint64(0)
+    _lib.check(_lib.lib().rnamc_mutant_plan(*head, C.byref(count), None, None, 0))
+    mp = np.empty(max(count.value, 1), dtype=np.uint32)
+    mb = np.empty(max(count.value, 1), dtype=np.uint8)
+    _lib.check(_lib.lib().rnamc_mutant_plan(*head, C.byref(count), mp.ctypes.data, mb.ctypes.data, count.value))
+    return mp[:count.value], mb[:count.value]
+
+
+def _mutant_scan(entry, handle, seq, uses_contra_model, allows_short_hairpins, positions, constraint, max_bp_span):
+    """rnamc_mutant_scan / _multi on `handle` -> MutantScan"""
+    seq = np.ascontiguousarray(seq, dtype=np.uint8)
+    n = int(seq.shape[0])
+    mp, mb = mutant_plan(seq, positions)
+    pos = _positions(positions)
+    cons = None
+    if constraint is not None:
+        cons = constraint.encode("ascii", errors="replace") if isinstance(constraint, str) else bytes(constraint)
+        if len(cons) != n:
+            raise _lib.RnamcError(_lib.ERR_INVALID_ARG, f"constraint has length {len(cons)}, the sequence {n}")
+    M = len(mp)
+    logz = np.empty(max(M, 1), dtype=np.float32)
+    q = np.empty(max(M, 1), dtype=np.int64)
+    dp = np.empty(max(M, 1), dtype=np.float32)
+    mi = np.empty(max(M, 1), dtype=np.uint32)
+    mj = np.empty(max(M, 1), dtype=np.uint32)
+    paired = np.empty((max(M, 1), n), dtype=np.float32)
+    wt_logz = C.c_float(0)
+    wt_paired = np.empty(n, dtype=np.float32)
+    _lib.check(entry(handle, seq.ctypes.data, n, cons, _span(max_bp_span), int(bool(uses_contra_model)),
+                     int(bool(allows_short_hairpins)), None if pos is None else pos.ctypes.data,
+                     0 if pos is None else len(pos), logz.ctypes.data, q.ctypes.data, dp.ctypes.data,
+                     mi.ctypes.data, mj.ctypes.data, paired.ctypes.data, C.byref(wt_logz), wt_paired.ctypes.data))
+    pair = np.stack([mi[:M], mj[:M]], axis=1).astype(np.int64)
+    pair[pair == 0xffffffff] = -1
+    return MutantScan(mp, mb, logz[:M], np.float32(wt_logz.value), q[:M], dp[:M], pair, paired[:M], wt_paired)
+
+
 # one rnamc_twoloop_score (include/rnamc.h)
 TWOLOOP_DTYPE = np.dtype([("i", "<u4"), ("j", "<u4"), ("k", "<u4"), ("l", "<u4"),
                           ("score", "<f4")])
@@ -543,6 +645,14 @@ class Context:
         return _bpp_windowed(_lib.lib().rnamc_bpp_windowed, self._h, seq, window, uses_contra_model,
                              allows_short_hairpins, stride, max_bp_span, constraint)
 
+    def mutant_scan(self, seq, uses_contra_model, allows_short_hairpins, positions=None, constraint=None,
+                    max_bp_span=0):
+        """Point-mutation scan of one sequence (rnamc_mutant_scan): every single-base mutant of
+        `positions` (None: all) folded and compared with the wild type on the device -> MutantScan.
+        constraint: None or the wild type's string over ". x ( ) < >", applied to every mutant."""
+        return _mutant_scan(_lib.lib().rnamc_mutant_scan, self._h, seq, uses_contra_model, allows_short_hairpins,
+                            positions, constraint, max_bp_span)
+
     def debug_fetch(self, seq_idx, which, n):
         out = np.empty((n, n), dtype=np.float32)
         _lib.check(_lib.lib().rnamc_debug_fetch(self._h, seq_idx, which, out.ctypes.data))
@@ -626,6 +736,14 @@ class Pool:
         (rnamc_bpp_windowed_multi): the same bits."""
         return _bpp_windowed(_lib.lib().rnamc_bpp_windowed_multi, self._h, seq, window, uses_contra_model,
                              allows_short_hairpins, stride, max_bp_span, constraint)
+
+
+    def mutant_scan(self, seq, uses_contra_model, allows_short_hairpins, positions=None, constraint=None,
+                    max_bp_span=0):
+        """As Context.mutant_scan, the mutant list sharded over the pool's contexts
+        (rnamc_mutant_scan_multi): the same bits in summation mode 0."""
+        return _mutant_scan(_lib.lib().rnamc_mutant_scan_multi, self._h, seq, uses_contra_model,
+                            allows_short_hairpins, positions, constraint, max_bp_span)
 
 
 def shard_plan(lengths, n_shards):
@@ -752,6 +870,17 @@ def mccaskill_algo_windowed(seq, window, uses_contra_model, allows_short_hairpin
     with _ctx_lock:
         return _pool_for(fold_score_sets).bpp_windowed(seq, window, uses_contra_model, allows_short_hairpins,
                                                        stride, max_bp_span, constraint)
+
+
+def mutant_scan(seq, uses_contra_model, allows_short_hairpins, fold_score_sets, positions=None, constraint=None,
+                max_bp_span=0):
+    """Point-mutation scan of one sequence (riboSNitch / SNPfold / RNAsnp / RNAmute): every
+    single-base mutant of `positions` (None: every base) folded over the process's devices and its
+    pair probabilities compared with the wild type's on the device -> MutantScan.  No triangle
+    reaches the host."""
+    with _ctx_lock:
+        return _pool_for(fold_score_sets).mutant_scan(seq, uses_contra_model, allows_short_hairpins, positions,
+                                                      constraint, max_bp_span)
 
 
 def structure_score(seq, dot_bracket, uses_contra_model, allows_short_hairpins, fold_score_sets):
