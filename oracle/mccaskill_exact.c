@@ -13,15 +13,17 @@
 #define ORACLE_EXACT 1
 #include "mccaskill_oracle.c"
 
-/* bpp_packed: n(n+1)/2 doubles, diagonal-major, absent = -1; *log_partition: ln Z */
-int rnamc_oracle_exact_bpp(const rnamc_params* p, const uint8_t* seq, uint32_t n,
-                           int uses_contra_model, int allows_short_hairpins, double* bpp_packed,
-                           double* log_partition) {
+/* bpp_packed: n(n+1)/2 doubles, diagonal-major, absent = -1; *log_partition: ln Z;
+ * mask: n x n row-major, 0 = the pair may not close, or NULL (ostate, mccaskill_oracle.c) */
+int rnamc_oracle_exact_bpp_masked(const rnamc_params* p, const uint8_t* seq, uint32_t n,
+                                  int uses_contra_model, int allows_short_hairpins,
+                                  const uint8_t* mask, double* bpp_packed, double* log_partition) {
   int st = check_args(p, seq, n);
   if (st) return st;
   ostate s;
   st = ostate_init(&s, n);
   if (st) return st;
+  s.mask = mask;
   int bad;
   if (uses_contra_model) {
     o_get_fold_sums_contra(p, seq, &s, allows_short_hairpins);
@@ -45,4 +47,11 @@ int rnamc_oracle_exact_bpp(const rnamc_params* p, const uint8_t* seq, uint32_t n
   }
   ostate_free(&s);
   return RNAMC_OK;
+}
+
+int rnamc_oracle_exact_bpp(const rnamc_params* p, const uint8_t* seq, uint32_t n,
+                           int uses_contra_model, int allows_short_hairpins, double* bpp_packed,
+                           double* log_partition) {
+  return rnamc_oracle_exact_bpp_masked(p, seq, n, uses_contra_model, allows_short_hairpins, NULL,
+                                       bpp_packed, log_partition);
 }

@@ -45,7 +45,14 @@ typedef struct {
   rnamc_twoloop_score* rec_twoloop;
   size_t rec_count, rec_cap;
   int rec_failed;
+  /* optional pair mask (the *_masked entries): n x n row-major, 0 = (i, j) may not close;
+   * NULL = none.  Set on the state after ostate_init, which leaves it NULL. */
+  const uint8_t* mask;
 } ostate;
+
+/* a masked pair is a canonical pair whose sums_close key is never inserted: everything
+ * downstream, the outside pass included, keys on sums_close > -inf */
+#define O_MASK_OK(s, i, j) (!(s)->mask || (s)->mask[IDX(i, j)])
 
 static void rec_twoloop(ostate* s, uint32_t i, uint32_t j, uint32_t k, uint32_t l, float y) {
   if (!s->rec_hairpin) return;
@@ -121,7 +128,8 @@ static void o_get_fold_sums(const rnamc_params* p, const uint8_t* seq, ostate* s
     for (uint32_t i = 0; i + subseq_len <= n; i++) {
       uint32_t j = i + subseq_len - 1;
       Score sum = ONEG_INF;
-      if (j - i + 1 >= RNAMC_MIN_SPAN_HAIRPIN_CLOSE && o_has_canonical_basepair(seq[i], seq[j])) {
+      if (j - i + 1 >= RNAMC_MIN_SPAN_HAIRPIN_CLOSE && o_has_canonical_basepair(seq[i], seq[j]) &&
+          O_MASK_OK(s, i, j)) {
         Score hairpin_score = o_get_hairpin_score(t, seq, i, j);
         if (s->rec_hairpin) s->rec_hairpin[IDX(i, j)] = hairpin_score; /* :302-304 */
         o_logsumexp(&sum, hairpin_score);
@@ -186,7 +194,7 @@ static void o_get_fold_sums_contra(const rnamc_params* p, const uint8_t* seq, os
     for (uint32_t i = 0; i + subseq_len <= n; i++) {
       uint32_t j = i + subseq_len - 1;
       Score sum = ONEG_INF;
-      if (o_has_canonical_basepair(seq[i], seq[j]) &&
+      if (o_has_canonical_basepair(seq[i], seq[j]) && O_MASK_OK(s, i, j) &&
           (allows_short_hairpins || j - i + 1 >= RNAMC_MIN_SPAN_HAIRPIN_CLOSE)) {
         if (j - i - 1 <= RNAMC_MAX_LOOP_LEN) {
           Score hairpin_score = o_get_hairpin_score_contra(f, seq, i, j);
@@ -383,15 +391,16 @@ static int check_args(const rnamc_params* p, const uint8_t* seq, uint32_t n) {
 #ifndef ORACLE_EXACT /* the exported entry points of the reference restatement */
 /* mccaskill_algo — mccaskill_algo.rs:247-280.  `mats`, if non-NULL, receives
  * copies of DP matrices (each n*n row-major, caller-allocated, entries may be
- * NULL) in the order of rnamc_debug_fetch's `which`. */
-int rnamc_oracle_bpp_dump(const rnamc_params* p, const uint8_t* seq, uint32_t n,
-                          int uses_contra_model, int allows_short_hairpins, float* bpp_packed,
-                          float* log_partition, float** mats) {
+ * NULL) in the order of rnamc_debug_fetch's `which`.  `mask`: see ostate. */
+static int bpp_dump_masked(const rnamc_params* p, const uint8_t* seq, uint32_t n,
+                           int uses_contra_model, int allows_short_hairpins, const uint8_t* mask,
+                           float* bpp_packed, float* log_partition, float** mats) {
   int st = check_args(p, seq, n);
   if (st) return st;
   ostate s;
   st = ostate_init(&s, n);
   if (st) return st;
+  s.mask = mask;
   int bad;
   if (uses_contra_model) {
     o_get_fold_sums_contra(p, seq, &s, allows_short_hairpins);
@@ -428,6 +437,23 @@ int rnamc_oracle_bpp_dump(const rnamc_params* p, const uint8_t* seq, uint32_t n,
   }
   ostate_free(&s);
   return RNAMC_OK;
+}
+
+int rnamc_oracle_bpp_dump(const rnamc_params* p, const uint8_t* seq, uint32_t n,
+                          int uses_contra_model, int allows_short_hairpins, float* bpp_packed,
+                          float* log_partition, float** mats) {
+  return bpp_dump_masked(p, seq, n, uses_contra_model, allows_short_hairpins, NULL, bpp_packed,
+                         log_partition, mats);
+}
+
+/* The reference's arithmetic with keys removed: hard constraints only
+ * remove pairs, so a constrained call is the reference's loops run with the forbidden pairs'
+ * sums_close keys absent.  `mask` n x n row-major, 0 = forbidden, or NULL; `mats` as above. */
+int rnamc_oracle_bpp_masked(const rnamc_params* p, const uint8_t* seq, uint32_t n,
+                            int uses_contra_model, int allows_short_hairpins, const uint8_t* mask,
+                            float* bpp_packed, float* log_partition, float** mats) {
+  return bpp_dump_masked(p, seq, n, uses_contra_model, allows_short_hairpins, mask, bpp_packed,
+                         log_partition, mats);
 }
 
 /* get_fold_sums / get_fold_sums_contra alone — mccaskill_algo.rs:282-378 / 380-516: the seven

@@ -83,7 +83,13 @@ static inline void o_logsumexp(Score* sum, Score x) {
   } else {
 #ifdef ORACLE_EXACT
     Score hi = *sum > x ? *sum : x, lo = *sum > x ? x : *sum;
+#ifdef ORACLE_MAXPLUS
+    /* max-plus semiring (mfe_exact.c): the sum over structures becomes their maximum */
+    (void)lo;
+    *sum = hi;
+#else
     *sum = hi + log1p(exp(lo - hi));
+#endif
 #else
     Score y = fminf(*sum, x);
     Score z = fmaxf(*sum, x) - y;

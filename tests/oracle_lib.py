@@ -29,6 +29,9 @@ def lib():
         L.rnamc_oracle_bpp_batch.argtypes = [vp, C.c_uint32, vp, vp, C.c_int, C.c_int, vp, vp, vp,
                                              C.c_uint32]
         L.rnamc_oracle_exact_bpp.argtypes = [vp, vp, C.c_uint32, C.c_int, C.c_int, vp, vp]
+        L.rnamc_oracle_bpp_masked.argtypes = [vp, vp, C.c_uint32, C.c_int, C.c_int, vp, vp, vp, vp]
+        L.rnamc_oracle_exact_bpp_masked.argtypes = [vp, vp, C.c_uint32, C.c_int, C.c_int, vp, vp, vp]
+        L.rnamc_oracle_mfe_exact.argtypes = [vp, vp, C.c_uint32, C.c_int, C.c_int, vp, vp]
         L.rnamc_oracle_bruteforce.argtypes = [vp, vp, C.c_uint32, C.c_int, C.c_int, vp, vp, vp]
         L.rnamc_oracle_fold_scores.argtypes = [vp, vp, C.c_uint32, C.c_int, C.c_int, vp, vp, vp,
                                                C.POINTER(vp), C.POINTER(C.c_uint64)]
@@ -79,6 +82,59 @@ def bpp_dump(params_ptr, seq, contra, short=False):
     _chk(lib().rnamc_oracle_bpp_dump(params_ptr, seq.ctypes.data, n, int(contra), int(short),
                                      out.ctypes.data, logz.ctypes.data, ptrs))
     return out, np.float32(logz[0]), mats
+
+
+def _mask_arg(mask, n):
+    """pair mask -> (n x n uint8 array to keep alive, pointer or None); 0 = the pair may not close"""
+    if mask is None:
+        return None, None
+    m = np.ascontiguousarray(mask, dtype=np.uint8)
+    assert m.shape == (n, n), (m.shape, n)
+    return m, m.ctypes.data
+
+
+def bpp_masked(params_ptr, seq, contra, short=False, mask=None, dump=False):
+    """The reference's arithmetic with the sums_close keys of the masked pairs absent
+    (rnamc_oracle_bpp_masked) -> (packed bpp f32, log partition f32[, 7 matrices as bpp_dump])"""
+    seq = np.ascontiguousarray(seq, dtype=np.uint8)
+    n = seq.shape[0]
+    keep, mptr = _mask_arg(mask, n)
+    out = np.empty(n * (n + 1) // 2, dtype=np.float32)
+    logz = np.zeros(1, dtype=np.float32)
+    mats = [np.empty((n, n), dtype=np.float32) for _ in range(7)] if dump else None
+    ptrs = (C.c_void_p * 7)(*[m.ctypes.data for m in mats]) if dump else None
+    _chk(lib().rnamc_oracle_bpp_masked(params_ptr, seq.ctypes.data, n, int(contra), int(short), mptr,
+                                       out.ctypes.data, logz.ctypes.data, ptrs))
+    del keep
+    if dump:
+        return out, np.float32(logz[0]), mats
+    return out, np.float32(logz[0])
+
+
+def exact_bpp_masked(params_ptr, seq, contra, short=False, mask=None):
+    """exact_bpp with the masked pairs removed -> (packed bpp f64, ln Z f64)"""
+    seq = np.ascontiguousarray(seq, dtype=np.uint8)
+    n = seq.shape[0]
+    keep, mptr = _mask_arg(mask, n)
+    out = np.empty(n * (n + 1) // 2, dtype=np.float64)
+    logz = np.zeros(1, dtype=np.float64)
+    _chk(lib().rnamc_oracle_exact_bpp_masked(params_ptr, seq.ctypes.data, n, int(contra), int(short),
+                                             mptr, out.ctypes.data, logz.ctypes.data))
+    del keep
+    return out, float(logz[0])
+
+
+def mfe_exact(params_ptr, seq, contra, short=False, mask=None):
+    """Score of the best structure: the inside loops in f64 under (max, +) (oracle/mfe_exact.c),
+    with the masked pairs removed -> f64"""
+    seq = np.ascontiguousarray(seq, dtype=np.uint8)
+    n = seq.shape[0]
+    keep, mptr = _mask_arg(mask, n)
+    best = np.zeros(1, dtype=np.float64)
+    _chk(lib().rnamc_oracle_mfe_exact(params_ptr, seq.ctypes.data, n, int(contra), int(short), mptr,
+                                      best.ctypes.data))
+    del keep
+    return float(best[0])
 
 
 FOLD_SUMS_FIELDS = ("sums_external", "sums_rightmost_basepairs_external",

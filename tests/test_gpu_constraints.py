@@ -3,7 +3,6 @@ constrained ln Z, pair probabilities and MFE against the enumeration of the comp
 structures; the 'x' identity P(p unpaired) = Z_{x@p} / Z at scale; everything forbidden; the
 consistency of keys, samples and MFE structures with the constraint; sampled frequencies against
 constraint_probability; batch invariance; error paths; the CLIs."""
-import ctypes as C
 import math
 import os
 import random
@@ -14,8 +13,8 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
-from test_constraints_cpu import allowed, parse, random_constraint
-from test_mfe_cpu import nested_structures
+from constraint_masks import allowed_matrix, enumerate_constrained, pairs_of, sscore, tol
+from test_constraints_cpu import allowed, random_constraint
 
 pytestmark = pytest.mark.gpu
 
@@ -64,55 +63,6 @@ def plain_bpp(ctx, seqs):
 
 def packed(mats):
     return np.concatenate([m.packed for m in mats])
-
-
-def pairs_of(db):
-    st, out = [], []
-    for q, ch in enumerate(db):
-        if ch == "(":
-            st.append(q)
-        elif ch == ")":
-            out.append((st.pop(), q))
-        else:
-            assert ch == "."
-    assert not st
-    return out
-
-
-def sscore(params, seq, db, contra, short):
-    from rna_algos_amd import _lib
-    seq = np.ascontiguousarray(seq, dtype=np.uint8)
-    out = C.c_double()
-    _lib.check(_lib.lib().rnamc_structure_score(params.ptr, seq.ctypes.data, len(seq), db.encode(),
-                                                int(contra), int(short), C.byref(out)))
-    return out.value
-
-
-def tol(w, db):
-    return 4 * (len(pairs_of(db)) + 1) * float(np.spacing(np.float32(max(1.0, abs(w)))))
-
-
-def allowed_matrix(c, span):
-    """allowed(c, span, i, j) for every i < j at once (the same rules, crossing pair by pair)"""
-    n = len(c)
-    _, pairs = parse(c)
-    arr = np.array(list(c))
-    ii, jj = np.indices((n, n))
-    ok = jj > ii
-    if span:
-        ok &= jj - ii + 1 <= span
-    ok[arr == "x", :] = False
-    ok[:, arr == "x"] = False
-    ok[arr == ">", :] = False
-    ok[:, arr == "<"] = False
-    for a, b in pairs:
-        ok[[a, b], :] = False
-        ok[:, [a, b]] = False
-        ok[:a, a + 1:b] = False      # i < a < j < b
-        ok[a + 1:b, b + 1:] = False  # a < i < b < j
-    for a, b in pairs:
-        ok[a, b] = not span or b - a + 1 <= span
-    return ok
 
 
 def mfe_score_tol(w, n_pairs):
@@ -168,29 +118,6 @@ def test_neutral_constraints_bit_identical(ctx, params, trnas, contra, short):
 
 
 # ---------------------------------------------------------------------------------------------------
-def enumerate_constrained(params, seq, cons, span, contra, short):
-    """(ln Z_c, {pair: p}, best score, best structures) over the nested structures of the model's
-    space that satisfy the constraint, in f64"""
-    from rna_algos_amd.mccaskill_algo import is_compatible
-    ws, dbs = [], []
-    for db in nested_structures(seq):
-        if not is_compatible(db, cons, span):
-            continue
-        w = sscore(params, seq, db, contra, short)
-        if w == -math.inf:
-            continue
-        ws.append(w)
-        dbs.append(db)
-    ws = np.array(ws, np.float64)
-    m = ws.max()
-    lz = m + math.log(np.exp(ws - m).sum())
-    probs = {}
-    for w, db in zip(ws, dbs):
-        for p in pairs_of(db):
-            probs[p] = probs.get(p, 0.0) + math.exp(w - lz)
-    return lz, probs, m, ws, dbs
-
-
 @pytest.mark.parametrize("contra,short", MODELS)
 def test_exhaustive_small(ctx, params, contra, short):
     from rna_algos_amd.mccaskill_algo import is_compatible

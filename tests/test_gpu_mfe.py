@@ -1,6 +1,7 @@
 """Maximum-score structure on the GPU (rnamc_mfe_batch): against the exhaustive maximum over every
 nested structure (host scorer rnamc_structure_score), against an independent f64 restatement
-(mfe_ref), dominance over Boltzmann samples and ln Z, local optimality, bit-identical invariance
+(mfe_ref), against the oracle's max-plus compile (oracle/mfe_exact.c) from one block per diagonal
+to five, unconstrained and under the mixed constraint, dominance over Boltzmann samples and ln Z, local optimality, bit-identical invariance
 under grouping, order, summation mode and neighbours, edge cases and the public layers."""
 import ctypes as C
 import os
@@ -10,7 +11,9 @@ import sys
 import numpy as np
 import pytest
 
+import helix_inputs
 import oracle_lib as O
+from constraint_masks import allowed_matrix, binds, mixed_case, reference, warm
 from mfe_ref import mfe_ref
 from test_mfe_cpu import nested_structures
 
@@ -93,6 +96,65 @@ def test_against_restatement(ctx, params, trnas, contra, short):
         assert abs(float(v) - m) <= t, (len(seq), v, m)
         assert abs(sscore(params, seq, db, contra, short) - m) <= t, (len(seq), m)
         assert abs(float(s) - m) <= t
+
+
+def check_optimum(params, seq, db, s, v, best, contra, short, what):
+    """the sweep's value, the traceback's score and the returned structure's own score all reach
+    `best` within the bound of test_dominance_and_local_optimality -> worst error / bound"""
+    t = tol(best, db) + 8 * float(np.spacing(np.float32(max(1.0, abs(best)))))
+    errs = (abs(float(v) - best), abs(float(s) - best), abs(sscore(params, seq, db, contra, short) - best))
+    assert max(errs) <= t, (what, "dp, score, structure_score off by", errs, "bound", t, "optimum", best)
+    return max(errs) / t
+
+
+def scale_inputs():
+    """one and two 256-lane blocks per diagonal and the walker's decision scans past 8 x 64 candidates;
+    a perfect hairpin (traceback stack depth); two helices sharing a G-run (ties)"""
+    seqs = [(f"splitmix n={n}", O.splitmix_seq(n, 31337 + n)) for n in (255, 256, 257, 300, 511, 512, 513, 640)]
+    seqs.append(("hairpin G300 A4 C300", np.array([2] * 300 + [0] * 4 + [1] * 300, np.uint8)))
+    seqs.append(("split_run(0)", helix_inputs.split_run(0)))
+    return seqs
+
+
+@pytest.mark.parametrize("contra,short", MODELS)
+def test_optimum_at_scale(ctx, params, contra, short):
+    names, seqs = zip(*scale_inputs())
+    dbs, sc, dp = mfe(ctx, seqs, contra, short)
+    worst = 0.0
+    for name, seq, db, s, v in zip(names, seqs, dbs, sc, dp):
+        best = O.mfe_exact(params.ptr, seq, contra, short)
+        worst = max(worst, check_optimum(params, seq, db, s, v, best, contra, short, name))
+    print(f"contra={contra} short={short}: n = 207 .. 640, worst error {worst:.3f} of the bound")
+
+
+@pytest.mark.parametrize("contra", [False, True])
+def test_optimum_five_blocks(ctx, params, contra):
+    seq = O.splitmix_seq(1025, 31337 + 1025)
+    (db,), (s,), (v,) = mfe(ctx, [seq], contra, False)
+    best = O.mfe_exact(params.ptr, seq, contra, False)
+    worst = check_optimum(params, seq, db, s, v, best, contra, False, "n=1025")
+    print(f"contra={contra}: n = 1025, error {worst:.3f} of the bound")
+
+
+@pytest.mark.parametrize("contra,short", MODELS)
+def test_constrained_optimum_at_scale(ctx, params, contra, short):
+    """the mixed constraint beside an unconstrained record (the call's span limit holds for both)"""
+    from rna_algos_amd.mccaskill_algo import is_compatible
+    worst = 0.0
+    sizes = (257, 400, 640)
+    warm(*[(reference, n, contra, short, constrained) for n in sizes for constrained in (False, True)])
+    for n in sizes:
+        seq, cons, span, mask = mixed_case(n)
+        ok, kc, kp = binds(reference(n, contra, short, True)[0], reference(n, contra, short, False)[0])
+        assert ok, f"n={n}: the constraint does not bind: {kc} of {kp} keys"
+        other = O.splitmix_seq(n - 31, 5300 + n)
+        dbs, sc, dp = ctx.mfe_batch([other, seq], contra, short, [None, cons], span)
+        for x, (q, c, m) in enumerate(((other, None, allowed_matrix("." * len(other), span)), (seq, cons, mask))):
+            db, s, v = dbs[x], sc[x], dp[x]
+            assert len(db) == len(q) and is_compatible(db, c, span), (n, db, c, span)
+            best = O.mfe_exact(params.ptr, q, contra, short, m)
+            worst = max(worst, check_optimum(params, q, db, s, v, best, contra, short, f"n={n} cons={c is not None}"))
+    print(f"contra={contra} short={short}: constrained, n = 257 .. 640, worst error {worst:.3f} of the bound")
 
 
 def admissible(seq, i, j, contra, short):
