@@ -222,6 +222,199 @@ def test_tree_order(ctx):
         reset(ctx)
 
 
+# ---- beyond d = 1024: the sixteen-wave form of the fill (launch_centroid_batch picks one wave per 64 cells
+# for d <= 64, four for d <= 1024, sixteen beyond), k scans of 16 steps and more in the traceback, the
+# `active` prefix shrinking on diagonals past 1024, chunk cuts between multi-megabyte items.
+# n = 1025 ends at d = 1024, the last four-wave launch; n = 1026 has exactly one cell at d = 1025;
+# n = 1100 has 75 sixteen-wave diagonals, on which the shorter items have dropped out of `active`.
+BIG_LENS = [1100, 1026, 1025, 700, 90]
+BIG_GAMMAS = [2.0, 8.0, 256.0]
+
+
+def big_batch():
+    from rna_algos_amd.workloads import synthetic_seq
+    return [synthetic_seq(n, seed=n) for n in BIG_LENS]
+
+
+def item_floats(n):
+    """centroid_item_floats (rnamc_device.h) restated: the n(n+1)/2 floats of an item's packed triangle,
+    rounded up to a multiple of 64"""
+    return (n * (n + 1) // 2 + 63) // 64 * 64
+
+
+@pytest.fixture(scope="module")
+def big_result(ctx):
+    """the five-record batch around d = 1024 through the entry with default knobs (shared, left unchanged)"""
+    reset(ctx)
+    seqs = big_batch()
+    res = ctx_raw(ctx, seqs, BIG_GAMMAS, False)
+    return seqs, res, ctx.stats()
+
+
+def test_launch_form_edge(ctx, big_result):
+    """Turner, mode 0, default knobs: every (s, g) of the batch around the four-wave / sixteen-wave edge
+    equals the oracle, and every record past 1024 nt has a fold that holds a pair"""
+    seqs, (strs, npairs, acc, logz, tris), _ = big_result
+    assert np.isfinite(logz).all()
+    assert_equal_oracle(seqs, BIG_GAMMAS, strs, npairs, acc, tris)
+    for s, n in enumerate(BIG_LENS):
+        if n > 1024:
+            assert any("(" in x for x in strs[s]), n
+
+
+def test_long_record_alone_equals_batch(ctx, big_result):
+    """the 1100-nt record alone (every launch has one item): the rows, counts and accuracy bits it has
+    inside the batch"""
+    seqs, (strs, npairs, acc, logz, tris), _ = big_result
+    reset(ctx)
+    strs1, npairs1, acc1, logz1, tris1 = ctx_raw(ctx, [seqs[0]], BIG_GAMMAS, False)
+    assert strs1[0] == strs[0]
+    assert np.array_equal(npairs1[0], npairs[0])
+    assert np.array_equal(acc1[0].view(np.uint32), acc[0].view(np.uint32))
+    assert logz1[0].view(np.uint32) == logz[0].view(np.uint32)
+    assert np.array_equal(tris1[0].view(np.uint32), tris[0].view(np.uint32))
+
+
+def test_contrafold_at_size(ctx):
+    """CONTRAfold once past d = 1024, beside a 300-nt record"""
+    from rna_algos_amd.workloads import synthetic_seq
+    reset(ctx)
+    seqs = [synthetic_seq(n, seed=n) for n in (1100, 300)]
+    gammas = [4.0, 64.0]
+    strs, npairs, acc, logz, tris = ctx_raw(ctx, seqs, gammas, True)
+    assert np.isfinite(logz).all()
+    assert_equal_oracle(seqs, gammas, strs, npairs, acc, tris)
+    assert any("(" in x for x in strs[0])
+
+
+def test_ties_at_size(ctx):
+    """repeats and alternating GC past 1024 nt, both models: the traceback's float equality tests with k
+    scans longer than 64 and bifurcations parked on the stack"""
+    from rna_algos_amd.utils import bytes2seq
+    reset(ctx)
+    texts = ["GGGAAACCC" * 123, "GC" * 520]
+    assert [len(t) for t in texts] == [1107, 1040]
+    seqs = [bytes2seq(t.encode()) for t in texts]
+    gammas = [1.0, 4.0, 1024.0]
+    for contra in (False, True):
+        strs, npairs, acc, _, tris = ctx_raw(ctx, seqs, gammas, contra)
+        assert_equal_oracle(seqs, gammas, strs, npairs, acc, tris)
+        assert any("(" in x for row in strs for x in row)
+
+
+def hairpin(length):
+    """G^s A^l C^s of the given length (l = 4 or 5) and the constraint string of its s nested pairs"""
+    loop = 4 + length % 2
+    s = (length - loop) // 2
+    return "G" * s + "A" * loop + "C" * s, "(" * s + "." * loop + ")" * s
+
+
+def test_every_wave_slice_decides_a_cell(ctx):
+    """The maximum over the splits k of a cell is highly redundant on natural inputs (any k in an unpaired
+    gap between two domains attains it), so a sixteen-wave join that loses one wave's partial maximum
+    passes the batches above.  Here it cannot: record r is two hairpins of 512 + r and 514 nt that abut,
+    with a constraint string that leaves only their nested pairs, so at gamma = 1024 the fold is both
+    stems and the top cell (0, n-1), at d = n - 1 > 1024, has ONE maximal candidate: the split after the
+    first hairpin, k = 511 + r.  Any other split cuts a stem pair of positive gain, a skip loses an outer
+    pair, and (0, n-1) itself is no pair.  Wave w takes the splits a = k - i = 1 + w (mod 16): the sixteen
+    records put the deciding split in each of the sixteen waves once.  expect_accuracy = M(0, n-1)."""
+    from rna_algos_amd.utils import bytes2seq
+    reset(ctx)
+    seqs, cons, firsts = [], [], []
+    for r in range(16):
+        a, ca = hairpin(512 + r)
+        b, cb = hairpin(514)
+        seqs.append(bytes2seq((a + b).encode()))
+        cons.append(ca + cb)
+        firsts.append(512 + r)
+    assert sorted((l1 - 2) % 16 for l1 in firsts) == list(range(16))  # a = l1 - 1 = 1 + w (mod 16)
+    assert min(len(s) for s in seqs) - 1 > 1024
+    gammas = [1024.0]
+    strs, npairs, acc, logz, tris = ctx_raw(ctx, seqs, gammas, False, cons=cons)
+    assert np.isfinite(logz).all()
+    for s, l1 in enumerate(firsts):
+        assert strs[s][0] == cons[s], l1  # every designed pair is in the fold, and nothing else can be
+    assert_equal_oracle(seqs, gammas, strs, npairs, acc, tris)
+
+
+def test_chunk_cuts_between_long_items(ctx, big_result):
+    """centroid_chunk_bytes = the bytes of two 1100-nt items: 2 * item_floats(1100) * 4 = 2 * 605 568 * 4
+    (a chunk takes items while the sum of their centroid_item_floats stays within the budget in floats, so
+    this value admits two such items and not a third).  Items go longest record first, thresholds in
+    order: the chunks are [1100, 1100], [1100, 1026], ... -- the thresholds of the 1100-nt and of the
+    1026-nt record land in different chunks.  Results equal the default-knob run bit for bit."""
+    seqs, (strs, npairs, acc, logz, tris), stats = big_result
+    assert item_floats(1100) == 605568
+    chunk_bytes = 2 * item_floats(1100) * 4
+    assert chunk_bytes // 4 >= 2 * item_floats(1100) and chunk_bytes // 4 < 3 * item_floats(1100)
+    assert item_floats(1100) + item_floats(1026) <= chunk_bytes // 4 < item_floats(1100) + 2 * item_floats(1026)
+    reset(ctx)
+    ctx.set("centroid_chunk_bytes", chunk_bytes)
+    try:
+        strs2, npairs2, acc2, logz2, tris2 = ctx_raw(ctx, seqs, BIG_GAMMAS, False)
+        stats2 = ctx.stats()
+    finally:
+        reset(ctx)
+    assert strs2 == strs
+    assert np.array_equal(npairs2, npairs)
+    assert np.array_equal(acc2.view(np.uint32), acc.view(np.uint32))
+    assert np.array_equal(logz2.view(np.uint32), logz.view(np.uint32))
+    for a, b in zip(tris2, tris):
+        assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
+    # the cut happened: every fold of the 1100-nt record is non-empty, so its three items went through the
+    # fill, and the third opens a second chunk of 1100 + 1 launches that the default run does not make
+    assert all("(" in x for x in strs[0])
+    print("launches_other", stats["launches_other"], "chunked", stats2["launches_other"])
+    assert stats2["launches_other"] >= stats["launches_other"] + 1101
+
+
+def test_tree_order_at_size(ctx):
+    """summation_mode 1, tree_lane 1, past d = 1024: every (s, g) equals the oracle on the triangles the
+    SAME call returned, as test_tree_order"""
+    from rna_algos_amd.workloads import synthetic_seq
+    seqs = [synthetic_seq(n, seed=n) for n in (1100, 1030)]
+    gammas = [2.0, 32.0]
+    try:
+        reset(ctx)
+        ctx.set("summation_mode", 1)
+        ctx.set("tree_lane", 1)
+        strs, npairs, acc, logz, tris = ctx_raw(ctx, seqs, gammas, False)
+        assert np.isfinite(logz).all()
+        assert_equal_oracle(seqs, gammas, strs, npairs, acc, tris)
+        assert all(any("(" in x for x in row) for row in strs)
+    finally:
+        ctx.set("tree_lane", 1)
+        reset(ctx)
+
+
+def test_trnas_short_hairpins(ctx, params, trnas):
+    """allows_short_hairpins = 1 (CONTRAfold): triangles and log_z equal mccaskill_algo_batch(seqs, True,
+    True)'s bit for bit, every (s, g) equals the oracle on them, and at gamma = 1024 some fold holds a pair
+    with j - i < 4 -- which the CPU oracle's fold of O.bpp(..., True, True) has too (the input condition)"""
+    import short_pairs as SP
+    from rna_algos_amd.mccaskill_algo import mccaskill_algo_batch
+    reset(ctx)
+    seqs = [s for _, s in trnas]
+    gammas = GRID + [0.5, 3.7]
+    assert gammas[17] == 1024.0
+    SP.assert_input_has_short_pairs(params, seqs)
+    cpu_short = 0
+    for s in seqs:
+        tri, _ = O.bpp(params.ptr, s, True, True)
+        pairs, _ = O.centroid_fold(np.where(tri < 0, np.float32(-1), tri).astype(np.float32), len(s), np.float32(1024.0))
+        cpu_short += sum(1 for i, j in pairs if j - i < 4)
+    assert cpu_short > 0
+    ref_mats, ref_logz = mccaskill_algo_batch(seqs, True, True, params)
+    strs, npairs, acc, logz, tris = ctx_raw(ctx, seqs, gammas, True, short=True)
+    assert np.array_equal(logz.view(np.uint32), ref_logz.view(np.uint32))
+    for t, r in zip(tris, ref_mats):
+        assert np.array_equal(t.view(np.uint32), r.packed.view(np.uint32))
+        assert SP.short_present(t, r.n) > 0
+    assert_equal_oracle(seqs, gammas, strs, npairs, acc, tris)
+    gpu_short = sum(1 for s in range(len(seqs)) for i, j in SP.pairs_of(strs[s][17]) if j - i < 4)
+    assert gpu_short > 0
+
+
 def test_constraints(ctx, params, trnas):
     """an x run, a bracket pair and max_bp_span = 40 on the tRNAs (mode 0): triangles equal the constrained
     mccaskill_algo_batch's bit for bit, folds equal the oracle's on them, every row is compatible"""

@@ -125,13 +125,13 @@ def check_against(res, n, seq, positions, wt, wt_z, tris, zs):
     assert np.all(res.dist2 == want_q.astype(np.float64) / Q)
 
 
-def run_case(ctx, n, contra=False, positions=None, cons=None, span=0, seq=None):
+def run_case(ctx, n, contra=False, positions=None, cons=None, span=0, seq=None, short=False):
     seq = seq_of(n) if seq is None else seq
     _, _, recs = mutants_of(seq, positions)
-    wt_mats, wt_z = ctx.bpp_batch([seq], contra, False, constraints=None if cons is None else [cons], max_bp_span=span)
-    mats, zs = ctx.bpp_batch(recs, contra, False, constraints=None if cons is None else [cons] * len(recs),
+    wt_mats, wt_z = ctx.bpp_batch([seq], contra, short, constraints=None if cons is None else [cons], max_bp_span=span)
+    mats, zs = ctx.bpp_batch(recs, contra, short, constraints=None if cons is None else [cons] * len(recs),
                              max_bp_span=span)
-    res = ctx.mutant_scan(seq, contra, False, positions=positions, constraint=cons, max_bp_span=span)
+    res = ctx.mutant_scan(seq, contra, short, positions=positions, constraint=cons, max_bp_span=span)
     check_against(res, n, seq, positions, np.asarray(wt_mats[0].packed), wt_z[0], [np.asarray(m.packed) for m in mats],
                   zs)
     return res, seq, recs
@@ -332,8 +332,7 @@ def test_tree_order_mode(ctx):
         reset(ctx)
 
 
-def test_against_the_cpu_oracle(ctx, params):
-    """n = 30, Turner, reference order: the yardstick fed with the CPU oracle's triangles"""
+def check_against_the_cpu_oracle(ctx, params, contra=False, short=False):
     import oracle_lib as O
     reset(ctx)
     n = 30
@@ -341,13 +340,54 @@ def test_against_the_cpu_oracle(ctx, params):
     _, _, recs = mutants_of(seq)
 
     def oracle(s):
-        ref, z = O.bpp(params.ptr, s, False, False)
+        ref, z = O.bpp(params.ptr, s, contra, short)
         return np.where(ref < 0, np.float32(-1), ref).astype(np.float32), z
     wt, wt_z = oracle(seq)
     tris, zs = zip(*(oracle(r) for r in recs))
-    res = ctx.mutant_scan(seq, False, False)
+    res = ctx.mutant_scan(seq, contra, short)
     check_against(res, n, seq, None, wt, wt_z, list(tris), zs)
     assert np.any(res.dist2_q > 0)
+    return res
+
+
+def test_against_the_cpu_oracle(ctx, params):
+    """n = 30, Turner, reference order: the yardstick fed with the CPU oracle's triangles"""
+    check_against_the_cpu_oracle(ctx, params)
+
+
+# ---- allows_short_hairpins = 1 (CONTRAfold): the triangles carry pairs of span 1, 2 and 3, and the
+# compare kernel meets moved cells on the first three diagonals
+
+def short_moves(res):
+    """the mutants whose largest change is at a pair with j - i < 4"""
+    moved = res.max_dp > 0
+    return int(np.count_nonzero(moved & (res.max_pair[:, 1] - res.max_pair[:, 0] < 4)))
+
+
+@pytest.mark.parametrize("n,positions", [(76, None), (91, [0, 45, 90])])
+def test_short_hairpins(ctx, params, n, positions):
+    """all positions at n = 76 and the ends and middle at n = 91 (two strips), against the yardstick fed by
+    the dense entry with the same flag.  The flag is seen -- the assertion used: some mutant's max_pair has
+    span < 4 (the yardstick on the CPU oracle's triangles names such a pair for 72 of the 228 mutants at
+    n = 76 and for 6 of the 9 at n = 91), which the scan without the flag never names; its paired_prob and
+    ln Z differ too."""
+    import short_pairs as SP
+    reset(ctx)
+    SP.assert_input_has_short_pairs(params, [seq_of(n)])
+    res, seq, _ = run_case(ctx, n, contra=True, positions=positions, short=True)
+    assert np.any(res.dist2_q > 0)
+    print("mutants whose max_pair has span < 4:", short_moves(res), "of", len(res))
+    assert short_moves(res) > 0
+    plain = ctx.mutant_scan(seq, True, False, positions=positions)
+    assert short_moves(plain) == 0
+    assert not same_bits(res.paired_prob, plain.paired_prob) and not same_bits(res.log_z, plain.log_z)
+
+
+def test_against_the_cpu_oracle_short_hairpins(ctx, params):
+    """n = 30 with O.bpp(..., True, True)"""
+    import short_pairs as SP
+    SP.assert_input_has_short_pairs(params, [seq_of(30)])
+    check_against_the_cpu_oracle(ctx, params, True, True)
 
 
 def test_errors_leave_the_context_usable(ctx):

@@ -36,7 +36,8 @@ def batch():
     return [synthetic_seq(n, seed=900 + n) for n in LENS]
 
 
-def sparse_raw(entry, handle, seqs, contra, min_prob, cons=None, span=0, cap=None, lists=True, two_only=False):
+def sparse_raw(entry, handle, seqs, contra, min_prob, cons=None, span=0, cap=None, lists=True, two_only=False,
+               short=False):
     """the C entry itself -> (status, dict): per-record (i, j, p) views, counts, starts, total,
     paired_prob per record, log partition.  cap None: a count-only call first sizes the arrays."""
     from rna_algos_amd import _lib
@@ -50,7 +51,7 @@ def sparse_raw(entry, handle, seqs, contra, min_prob, cons=None, span=0, cap=Non
     paired = np.full(max(int(offsets[-1]), 1), np.nan, dtype=np.float32)
     logz = np.full(max(ns, 1), np.nan, dtype=np.float32)
     total = C.c_uint64(2 ** 63)
-    head = (handle, ns, bases.ctypes.data, offsets.ctypes.data, cb, span, int(contra), 0, float(min_prob))
+    head = (handle, ns, bases.ctypes.data, offsets.ctypes.data, cb, span, int(contra), int(short), float(min_prob))
     if lists and cap is None:
         _lib.check(entry(*head, None, count.ctypes.data, None, None, None, 0, C.byref(total), None, None))
         cap = int(total.value)
@@ -182,6 +183,111 @@ def test_independent_of_schedule(ctx, case):
             assert np.array_equal(a.view(np.uint32), b.view(np.uint32)), LENS[x]
         assert np.array_equal(res["paired"][pos].view(np.uint32), base["paired"][x].view(np.uint32))
         assert res["logz"][pos].view(np.uint32) == base["logz"][x].view(np.uint32)
+
+
+# ---- beyond 256 blocks a record: k_sparse_scan scans a record's block counts 256 blocks a step and carries
+# the running sum between steps.  361 nt: 65 341 cells, exactly 256 blocks, one full step; 362 nt: 65 703
+# cells, 257 blocks, one block in the second step; 724 nt: 262 450 cells, 1026 blocks, four full steps and
+# two blocks; the short records leave early (blockIdx.x >= n_blocks) beside the long ones.
+LENS_BIG = [361, 23, 724, 362, 5, 300]
+MIN_PROBS_BIG = [0.0, 1e-3, 0.5]
+
+
+def blocks_of(n):
+    return -(-(n * (n + 1) // 2) // 256)
+
+
+def batch_big():
+    from rna_algos_amd.workloads import synthetic_seq
+    assert [(n * (n + 1) // 2, blocks_of(n)) for n in (361, 362, 724)] == \
+        [(65341, 256), (65703, 257), (262450, 1026)]
+    assert 1026 == 4 * 256 + 2 and all(blocks_of(n) < 256 for n in (23, 5, 300))
+    return [synthetic_seq(n, seed=900 + n) for n in LENS_BIG]
+
+
+_dense_big_cache = {}
+
+
+def dense_big(ctx, contra, mode):
+    """the dense yardstick of the LENS_BIG batch, once per (model, mode), shared and left unchanged"""
+    key = (contra, mode)
+    if key not in _dense_big_cache:
+        reset(ctx)
+        ctx.set("summation_mode", mode)
+        try:
+            _dense_big_cache[key] = ctx.bpp_batch(batch_big(), contra, False)
+        finally:
+            reset(ctx)
+    return _dense_big_cache[key]
+
+
+def assert_equals_dense(res, mats, logz, min_prob):
+    assert_lists_equal(res["lists"], mats, min_prob)
+    assert_disjoint(res)
+    assert np.array_equal(res["logz"].view(np.uint32), logz.view(np.uint32))
+    for s, m in enumerate(mats):
+        assert np.array_equal(res["paired"][s].view(np.uint32), replay_paired(m.packed, m.n).view(np.uint32)), m.n
+        if min_prob == 0.0:
+            assert int(res["count"][s]) == int(np.sum(m.packed > -0.5)), m.n
+
+
+@pytest.mark.parametrize("contra,mode", [(False, 0), (True, 0), (False, 1)])
+def test_carry_across_scan_steps(ctx, contra, mode):
+    """both models in mode 0 (and Turner in mode 1, against the dense entry in that mode) x three thresholds:
+    lists, paired_prob and log_partition of records of 256, 257 and 1026 blocks equal the dense entry's,
+    bit for bit; at min_prob = 0 the count is the number of present cells"""
+    seqs = batch_big()
+    mats, logz = dense_big(ctx, contra, mode)
+    reset(ctx)
+    ctx.set("summation_mode", mode)
+    try:
+        for min_prob in MIN_PROBS_BIG:
+            res = ctx_sparse(ctx, seqs, contra, min_prob)
+            assert_equals_dense(res, mats, logz, min_prob)
+            # the records past one scan step list cells of blocks past the first 256 (or the carry is not seen)
+            for s, n in enumerate(LENS_BIG):
+                if blocks_of(n) > 256 and min_prob == 0.0:
+                    pi, pj, _ = res["lists"][s]
+                    d = pj.astype(np.int64) - pi
+                    assert np.any(d * n - d * (d - 1) // 2 + pi >= 256 * 256), n
+    finally:
+        reset(ctx)
+
+
+@pytest.mark.parametrize("case", ["groups_of_1", "reversed"])
+def test_carry_independent_of_schedule(ctx, case):
+    """the LENS_BIG batch one record a group, and reversed: the per-record bits do not change"""
+    seqs = batch_big()
+    mats, logz = dense_big(ctx, False, 0)
+    reset(ctx)
+    order = list(range(len(seqs)))
+    if case == "groups_of_1":
+        ctx.set("group_max_seqs", 1)
+    else:
+        order.reverse()
+    try:
+        res = ctx_sparse(ctx, [seqs[x] for x in order], False, 1e-3)
+    finally:
+        reset(ctx)
+    assert_equals_dense(res, [mats[x] for x in order], logz[order], 1e-3)
+
+
+def test_short_hairpins(ctx, params):
+    """allows_short_hairpins = 1 (CONTRAfold), the LENS batch, mode 0: the results equal the dense entry's
+    with the same flag, and pairs of span 1, 2 and 3 -- which exist under this flag alone -- are listed"""
+    import short_pairs as SP
+    seqs = batch()
+    SP.assert_input_has_short_pairs(params, [s for s in seqs if len(s) >= 5])
+    reset(ctx)
+    mats, logz = ctx.bpp_batch(seqs, True, True)
+    for min_prob in (0.0, 1e-3):
+        res = ctx_sparse(ctx, seqs, True, min_prob, short=True)
+        assert_equals_dense(res, mats, logz, min_prob)
+        spans = np.concatenate([pj.astype(np.int64) - pi for pi, pj, _ in res["lists"]])
+        for d in (1, 2, 3):
+            assert np.any(spans == d), (min_prob, d)
+    plain = ctx_sparse(ctx, seqs, True, 0.0)
+    assert not any(np.any(pj.astype(np.int64) - pi < 4) for pi, pj, _ in plain["lists"])
 
 
 def test_capacity_protocol(ctx):

@@ -86,21 +86,21 @@ def yardstick(n, starts, wl, B, tris):
     return band, paired
 
 
-def dense_windows(ctx, seq, starts, wl, B, contra, cons=None):
+def dense_windows(ctx, seq, starts, wl, B, contra, cons=None, short=False):
     """the dense entry on the window list with max_bp_span = B -> (packed triangles, ln Z)"""
     seqs = [seq[a:a + wl] for a in starts]
     cs = None if cons is None else [cons[a:a + wl] for a in starts]
-    mats, logz = ctx.bpp_batch(seqs, contra, False, constraints=cs, max_bp_span=B)
+    mats, logz = ctx.bpp_batch(seqs, contra, short, constraints=cs, max_bp_span=B)
     return [np.asarray(m.packed) for m in mats], logz
 
 
-def run_case(ctx, n, w, s, span=0, contra=False, cons=None, seq=None):
+def run_case(ctx, n, w, s, span=0, contra=False, cons=None, seq=None, short=False):
     seq = seq_of(n) if seq is None else seq
     starts, wl = windows(n, w, s)
     B = band_of(n, w, span)
-    tris, logz = dense_windows(ctx, seq, starts, wl, B, contra, cons)
+    tris, logz = dense_windows(ctx, seq, starts, wl, B, contra, cons, short)
     want_band, want_paired = yardstick(n, starts, wl, B, tris)
-    res = ctx.bpp_windowed(seq, w, contra, False, stride=s, max_bp_span=span, constraint=cons)
+    res = ctx.bpp_windowed(seq, w, contra, short, stride=s, max_bp_span=span, constraint=cons)
     assert res.band.shape == (n, B) and res.starts.tolist() == starts
     assert np.array_equal(res.band.view(np.uint32), want_band.view(np.uint32)), (n, w, s, span, contra)
     assert np.array_equal(res.paired_prob.view(np.uint32), want_paired.view(np.uint32)), (n, w, s, span, contra)
@@ -250,9 +250,7 @@ def test_tree_order_mode(ctx):
         reset(ctx)
 
 
-def test_against_the_cpu_oracle(ctx, params):
-    """(40, 12, 2), Turner, reference order: the yardstick fed with the CPU oracle's bpp of every window (B = W:
-    the span limit admits every pair of a window)"""
+def check_against_the_cpu_oracle(ctx, params, contra=False, short=False):
     import oracle_lib as O
     reset(ctx)
     n, w, s = 40, 12, 2
@@ -260,15 +258,69 @@ def test_against_the_cpu_oracle(ctx, params):
     starts, wl = windows(n, w, s)
     tris, zs = [], []
     for a in starts:
-        ref, z = O.bpp(params.ptr, seq[a:a + wl], False, False)
+        ref, z = O.bpp(params.ptr, seq[a:a + wl], contra, short)
         tris.append(np.where(ref < 0, np.float32(-1), ref).astype(np.float32))
         zs.append(z)
     want_band, want_paired = yardstick(n, starts, wl, w, tris)
-    res = ctx.bpp_windowed(seq, w, False, False, stride=s)
+    res = ctx.bpp_windowed(seq, w, contra, short, stride=s)
     assert np.count_nonzero(want_band > 0) > 0
     assert np.array_equal(res.band.view(np.uint32), want_band.view(np.uint32))
     assert np.array_equal(res.paired_prob.view(np.uint32), want_paired.view(np.uint32))
     assert np.array_equal(res.window_log_z.view(np.uint32), np.asarray(zs, np.float32).view(np.uint32))
+    return res, seq
+
+
+def test_against_the_cpu_oracle(ctx, params):
+    """(40, 12, 2), Turner, reference order: the yardstick fed with the CPU oracle's bpp of every window (B = W:
+    the span limit admits every pair of a window)"""
+    check_against_the_cpu_oracle(ctx, params)
+
+
+# ---- allows_short_hairpins = 1 (CONTRAfold): the windows' triangles carry pairs of span 1, 2 and 3
+
+SHORT_SHAPES = [(6, 5, 1), (38, 16, 3), (130, 65, 7)]
+
+
+@pytest.mark.parametrize("shape", SHORT_SHAPES)
+def test_short_hairpins(ctx, params, shape):
+    """two windows of the first admissible length, a final window off the stride grid, and a 65-wide band,
+    against the dense entry with the same flag; the columns d = 1, 2, 3 of the band hold present cells.
+    The input condition from the oracle alone: the exact ensemble of the sequence expects at least one pair
+    with j - i < 4 (3.34 at n = 38, 8.07 at n = 130).  The 6-nt sequence is too short for that -- its
+    ensemble expects 0.43 -- so for it the condition is that such pairs exist at all (expectation > 0)."""
+    import short_pairs as SP
+    reset(ctx)
+    n = shape[0]
+    e = SP.expected_short_pairs(params, seq_of(n))
+    assert e >= 1.0 if n > 6 else e > 0.0, e
+    res, *_ = run_case(ctx, *shape, contra=True, short=True)
+    assert np.any(res.band[:, 1:4] > -0.5)
+    assert np.all(res.band[:, 0] == -1)
+
+
+def test_against_the_cpu_oracle_short_hairpins(ctx, params):
+    """(40, 12, 2) with O.bpp(..., True, True) of every window"""
+    import short_pairs as SP
+    SP.assert_input_has_short_pairs(params, [seq_of(40)])
+    res, _ = check_against_the_cpu_oracle(ctx, params, True, True)
+    assert np.any(res.band[:, 1:4] > -0.5)
+
+
+@pytest.mark.parametrize("span", [2, 3, 4])
+def test_narrow_span_limits(ctx, params, span):
+    """max_bp_span = 2, 3, 4 admits the spans j - i < 2, 3, 4 alone, which only exist with the flag: (60, 16,
+    2) has a band of that width whose d = 1 column holds present cells; without the flag every cell of the
+    band is -1 and paired_prob is all zero"""
+    import short_pairs as SP
+    reset(ctx)
+    SP.assert_input_has_short_pairs(params, [seq_of(60)])
+    res, *_ = run_case(ctx, 60, 16, 2, span=span, contra=True, short=True)
+    assert res.band.shape == (60, span)
+    assert np.any(res.band[:, 1] > -0.5)
+    assert np.any(res.paired_prob > 0)
+    plain, *_ = run_case(ctx, 60, 16, 2, span=span, contra=True, short=False)
+    assert plain.band.shape == (60, span)
+    assert np.all(plain.band == -1) and np.all(plain.paired_prob.view(np.uint32) == 0)
 
 
 def test_window_log_partition(ctx):
