@@ -6,34 +6,11 @@ using namespace rnamc;
 
 namespace rnamc {
 
-// Grow-only device buffer: `need` bytes at least (an eighth of headroom when it fits).
-hipError_t grow_device(void** p, uint64_t* cap, uint64_t need) {
-  if (*cap >= need && *p) return hipSuccess;
-  if (*p) {
-    (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-  }
-  const uint64_t want = std::max<uint64_t>(need + need / 8, 4096);
-  hipError_t e = hipMalloc(p, want);
-  if (e != hipSuccess) {  // the headroom is optional
-    e = hipMalloc(p, std::max<uint64_t>(need, 1));
-    if (e == hipSuccess) *cap = std::max<uint64_t>(need, 1);
-    return e;
-  }
-  *cap = want;
-  return hipSuccess;
-}
-
 int ensure_ws(rnamc_ctx* c, uint64_t floats) {
   if (c->ws_floats >= floats) return RNAMC_OK;
-  if (c->d_ws) {
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipFree(c->d_ws));
-    c->d_ws = nullptr;
-    c->ws_floats = 0;
-  }
-  HIPCHK(hipMalloc(&c->d_ws, floats * sizeof(float)));
+  if (c->d_ws) HIPCHK(hipDeviceSynchronize());  // earlier work may still use the old one
+  c->ws_floats = 0;
+  HIPCHK(c->d_ws.replace_exact(floats));
   c->ws_floats = floats;
   return RNAMC_OK;
 }
@@ -86,17 +63,17 @@ int rnamc_ctx_create(const rnamc_params* params, int device, uint64_t workspace_
     rnamc_ctx_destroy(c);
     return rc;
   };
-  if (hipMalloc(&c->d_params, sizeof(rnamc_params)) != hipSuccess) return fail(RNAMC_ERR_OOM);
+  if (c->d_params.replace_exact(1) != hipSuccess) return fail(RNAMC_ERR_OOM);
   if (hipMemcpy(c->d_params, params, sizeof(rnamc_params), hipMemcpyHostToDevice) != hipSuccess)
     return fail(RNAMC_ERR_HIP);
-  if (hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking) != hipSuccess)
+  if (hipStreamCreateWithFlags(c->own_stream.put(), hipStreamNonBlocking) != hipSuccess)
     return fail(RNAMC_ERR_HIP);
   {
     // the pair-tail kernel carries the longest dependent chains of a diagonal: its few
     // workgroups should be placed first, the other kernel fills the rest of the chip
     int lo = 0, hi = 0;
     (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-    if (hipStreamCreateWithPriority(&c->aux_stream, hipStreamNonBlocking, hi) != hipSuccess)
+    if (hipStreamCreateWithPriority(c->aux_stream.put(), hipStreamNonBlocking, hi) != hipSuccess)
       return fail(RNAMC_ERR_HIP);
 #ifndef RNAMC_DBG_LAZY_BULK
     // the tree-order mode's side stream (mid-field products, lowest priority) is created HERE,
@@ -105,18 +82,11 @@ int rnamc_ctx_create(const rnamc_params* params, int device, uint64_t workspace_
     // this runtime and its 100-600 us kernels sit in the queue of the sweep's 11 us launches
     // (measured: the n = 4096 tree-order sweep took 157 ms instead of 49.5 ms at the end of
     // bench.py's batch run)
-    if (hipStreamCreateWithPriority(&c->bulk_stream, hipStreamNonBlocking, lo) != hipSuccess)
+    if (hipStreamCreateWithPriority(c->bulk_stream.put(), hipStreamNonBlocking, lo) != hipSuccess)
       return fail(RNAMC_ERR_HIP);
 #endif
   }
-  for (int x = 0; x < 16; x++) {
-    hipEvent_t ea = nullptr, eb = nullptr;
-    if (hipEventCreateWithFlags(&ea, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&eb, hipEventDisableTiming) != hipSuccess)
-      return fail(RNAMC_ERR_HIP);
-    c->ev_a.push_back(ea);
-    c->ev_b.push_back(eb);
-  }
+  if (c->ev_a.grow(16) != hipSuccess || c->ev_b.grow(16) != hipSuccess) return fail(RNAMC_ERR_HIP);
   if (workspace_bytes) {
     int rc = ensure_ws(c, workspace_bytes / 4);
     if (rc) return fail(rc);
@@ -127,66 +97,9 @@ int rnamc_ctx_create(const rnamc_params* params, int device, uint64_t workspace_
 
 void rnamc_ctx_destroy(rnamc_ctx* c) {
   if (!c) return;
-  {
-    DeviceGuard guard(c->device);
-    (void)hipDeviceSynchronize();
-    for (hipEvent_t e : c->events) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->kev) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->ev_a) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->ev_b) (void)hipEventDestroy(e);
-    if (c->aux_stream) (void)hipStreamDestroy(c->aux_stream);
-    if (c->bulk_stream) (void)hipStreamDestroy(c->bulk_stream);
-    for (hipEvent_t e : c->ev_a2) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->ev_b2) (void)hipEventDestroy(e);
-    if (c->ev_dual) (void)hipEventDestroy(c->ev_dual);
-
-    if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-    if (c->st_bases) (void)hipFree(c->st_bases);
-    for (int k = 0; k < 2; k++) {
-      if (c->st_out[k]) (void)hipFree(c->st_out[k]);
-      if (c->pinned[k]) (void)hipHostFree(c->pinned[k]);
-      if (c->pinned_ev[k]) (void)hipEventDestroy(c->pinned_ev[k]);
-      if (c->group_done[k]) (void)hipEventDestroy(c->group_done[k]);
-    }
-    if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
-    if (c->st_logz) (void)hipFree(c->st_logz);
-    if (c->d_params) (void)hipFree(c->d_params);
-    if (c->d_hp_init) (void)hipFree(c->d_hp_init);
-    if (c->d_ws) (void)hipFree(c->d_ws);
-    if (c->d_seqs) (void)hipFree(c->d_seqs);
-    if (c->d_tseqs) (void)hipFree(c->d_tseqs);
-    if (c->d_tree_tabs) (void)hipFree(c->d_tree_tabs);
-    if (c->sm_rows) (void)hipFree(c->sm_rows);
-    if (c->sm_w) (void)hipFree(c->sm_w);
-    if (c->sm_stack) (void)hipFree(c->sm_stack);
-    if (c->sm_rowoff) (void)hipFree(c->sm_rowoff);
-    if (c->mf_dp) (void)hipFree(c->mf_dp);
-    if (c->cf_items) (void)hipFree(c->cf_items);
-    if (c->cf_np) (void)hipFree(c->cf_np);
-    if (c->cf_acc) (void)hipFree(c->cf_acc);
-    if (c->st_cons) (void)hipFree(c->st_cons);
-    if (c->sp_items) (void)hipFree(c->sp_items);
-    if (c->sp_totals) (void)hipFree(c->sp_totals);
-    if (c->sp_i) (void)hipFree(c->sp_i);
-    if (c->sp_j) (void)hipFree(c->sp_j);
-    if (c->sp_p) (void)hipFree(c->sp_p);
-    if (c->sp_paired) (void)hipFree(c->sp_paired);
-    if (c->wn_items) (void)hipFree(c->wn_items);
-    if (c->wn_sum) (void)hipFree(c->wn_sum);
-    if (c->wn_cnt) (void)hipFree(c->wn_cnt);
-    if (c->wn_band) (void)hipFree(c->wn_band);
-    if (c->wn_paired) (void)hipFree(c->wn_paired);
-    for (hipEvent_t e : c->wn_events) (void)hipEventDestroy(e);
-    if (c->mt_wt) (void)hipFree(c->mt_wt);
-    if (c->mt_wt_paired) (void)hipFree(c->mt_wt_paired);
-    if (c->mt_items) (void)hipFree(c->mt_items);
-    if (c->mt_pitems) (void)hipFree(c->mt_pitems);
-    if (c->mt_sum) (void)hipFree(c->mt_sum);
-    if (c->mt_key) (void)hipFree(c->mt_key);
-    if (c->mt_paired) (void)hipFree(c->mt_paired);
-    for (hipEvent_t e : c->mt_events) (void)hipEventDestroy(e);
-  }
-  delete c;
+  DeviceGuard guard(c->device);
+  (void)hipDeviceSynchronize();
+  delete c;  // every member releases what it owns: with the context's device current, after the sync
 }
 
 int rnamc_ctx_set_params(rnamc_ctx* c, const rnamc_params* params) {

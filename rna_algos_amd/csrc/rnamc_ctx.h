@@ -1,6 +1,11 @@
 // rnamc_ctx.h — the device context behind the C ABI and what the host translation units that work
 // on it share: rnamc_ctx.cpp (life cycle, knobs, statistics), rnamc_sweep.cpp (batch plan and the
 // reference-order sweep), rnamc_sweep_tree.cpp (tree-order sweep), rnamc_entries.cpp (the entries).
+//
+// Every device buffer, pinned chunk, event and stream of the context is a member of an owner type
+// (DevBuf, PinnedBuf, Event, EventRing, Stream): non-copyable, released by its destructor, read at a
+// call site as the plain pointer or handle.  An entry that needs device state adds one member to
+// rnamc_ctx and nothing else; rnamc_ctx_destroy deletes the context and names no resource.
 #ifndef RNAMC_CTX_H
 #define RNAMC_CTX_H
 
@@ -34,6 +39,129 @@
     }                                                                                      \
   } while (0)
 
+namespace rnamc {
+
+// A device buffer and its capacity in bytes.
+template <class T>
+struct DevBuf {
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { (void)reset(); }
+  operator T*() const { return p; }
+  T* get() const { return p; }
+  uint64_t bytes() const { return cap; }
+  hipError_t reset() {  // free now
+    const hipError_t e = p ? hipFree(p) : hipSuccess;
+    p = nullptr;
+    cap = 0;
+    return e;
+  }
+  // free, then allocate exactly `count` elements (callers with sizing and sync rules of their own)
+  hipError_t replace_exact(uint64_t count) {
+    if (hipError_t e = reset()) return e;
+    return alloc(count * sizeof(T));
+  }
+  // grow-only: `count` elements at least (an eighth of headroom when it fits)
+  hipError_t grow(uint64_t count) {
+    const uint64_t need = count * sizeof(T);
+    if (p && cap >= need) return hipSuccess;
+    (void)reset();
+    if (alloc(std::max<uint64_t>(need + need / 8, 4096)) == hipSuccess) return hipSuccess;
+    return alloc(std::max<uint64_t>(need, 1));  // the headroom is optional
+  }
+  // grow, then copy `count` elements of host memory behind the work of `st`
+  hipError_t upload(const T* h, uint64_t count, hipStream_t st) {
+    if (hipError_t e = grow(count)) return e;
+    return hipMemcpyAsync(p, h, count * sizeof(T), hipMemcpyHostToDevice, st);
+  }
+
+ private:
+  hipError_t alloc(uint64_t n_bytes) {
+    const hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), n_bytes);
+    if (e == hipSuccess) cap = n_bytes;
+    return e;
+  }
+  T* p = nullptr;
+  uint64_t cap = 0;
+};
+
+// A pinned host chunk (hipHostMalloc), allocated once.
+struct PinnedBuf {
+  PinnedBuf() = default;
+  PinnedBuf(const PinnedBuf&) = delete;
+  PinnedBuf& operator=(const PinnedBuf&) = delete;
+  ~PinnedBuf() {
+    if (p) (void)hipHostFree(p);
+  }
+  operator float*() const { return p; }
+  hipError_t alloc(uint64_t floats) {
+    return hipHostMalloc(reinterpret_cast<void**>(&p), floats * sizeof(float), hipHostMallocDefault);
+  }
+
+ private:
+  float* p = nullptr;
+};
+
+// One event or stream.  The owner creates nothing by itself: whoever needs the handle creates it
+// into put(), when and how it wants it (the order in which a process creates its streams matters:
+// rnamc_ctx_create).
+template <class H, hipError_t (*Destroy)(H)>
+struct Handle {
+  Handle() = default;
+  Handle(const Handle&) = delete;
+  Handle& operator=(const Handle&) = delete;
+  ~Handle() {
+    if (h) (void)Destroy(h);
+  }
+  operator H() const { return h; }
+  H* put() { return &h; }
+
+ private:
+  H h = nullptr;
+};
+using Event = Handle<hipEvent_t, hipEventDestroy>;
+using Stream = Handle<hipStream_t, hipStreamDestroy>;
+
+// A grow-only ring of events of one kind (timed unless the flags say hipEventDisableTiming).  A
+// launch loop reads it through data(): plain handles.
+struct EventRing {
+  explicit EventRing(unsigned event_flags = hipEventDefault) : flags(event_flags) {}
+  EventRing(const EventRing&) = delete;
+  EventRing& operator=(const EventRing&) = delete;
+  ~EventRing() {
+    for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+  }
+  size_t size() const { return ev.size(); }
+  const hipEvent_t* data() const { return ev.data(); }
+  hipEvent_t operator[](size_t x) const { return ev[x]; }
+  hipError_t grow(size_t count) {
+    while (ev.size() < count) {
+      hipEvent_t e = nullptr;
+      if (hipError_t err = hipEventCreateWithFlags(&e, flags)) return err;
+      ev.push_back(e);
+    }
+    return hipSuccess;
+  }
+  // profiling: pair p = events 2p, 2p + 1 around an entry's own kernels; the milliseconds of the
+  // first `pairs` pairs added to *ms once their stream is drained
+  hipError_t pairs(size_t pairs) { return grow(2 * pairs); }
+  hipError_t pairs_ms(size_t pairs, double* ms) const {
+    for (size_t p = 0; p < pairs; p++) {
+      float t = 0.f;
+      if (hipError_t err = hipEventElapsedTime(&t, ev[2 * p], ev[2 * p + 1])) return err;
+      *ms += t;
+    }
+    return hipSuccess;
+  }
+
+ private:
+  std::vector<hipEvent_t> ev;
+  unsigned flags;
+};
+
+}  // namespace rnamc
+
 // Options of one sweep; the defaults are the unconstrained full sweep.
 struct SweepOpts {
   bool inside_only = false;  // no outside sweep (reference order whatever summation_mode says)
@@ -45,34 +173,31 @@ struct SweepOpts {
 struct rnamc_ctx {
   int device = 0;
   rnamc_params host_params;
-  rnamc_params* d_params = nullptr;
-  float* d_hp_init = nullptr;
+  rnamc::DevBuf<rnamc_params> d_params;
+  rnamc::DevBuf<float> d_hp_init;
   std::vector<float> h_hp_init;  // host copy, for rnamc_fold_scores
   uint32_t hp_init_len = 0;
-  float* d_ws = nullptr;
+  rnamc::DevBuf<float> d_ws;  // the workspace (ensure_ws)
   uint64_t ws_floats = 0;
-  rnamc::SeqDesc* d_seqs = nullptr;
-  uint64_t seqs_cap = 0;
-  rnamc::TreeSeq* d_tseqs = nullptr;  // descriptors of the tree-order mode
-  uint64_t tseqs_cap = 0;
+  rnamc::DevBuf<rnamc::SeqDesc> d_seqs;
+  rnamc::DevBuf<rnamc::TreeSeq> d_tseqs;  // descriptors of the tree-order mode
   std::vector<rnamc::TreeSeq> h_tseqs;  // (host copy: source of an async upload, must outlive it)
-  rnamc::TreeTabs* d_tree_tabs = nullptr;  // 2-loop tables of the tree-order mode (built from the params)
+  rnamc::DevBuf<rnamc::TreeTabs> d_tree_tabs;  // 2-loop tables of the tree-order mode (built from the params)
   bool tree_tabs_valid = false;
   // host-buffer entry: device staging of bases / result / log partition (grow-only)
   // The result is staged per lock-step GROUP in two alternating device buffers: group g's
   // D2H (copy stream, pinned bounce chunks, a host thread) runs while group g+1 sweeps.
-  uint8_t* st_bases = nullptr;
-  float* st_out[2] = {nullptr, nullptr};
-  float* st_logz = nullptr;
-  uint64_t st_bases_cap = 0, st_out_cap[2] = {0, 0}, st_logz_cap = 0;
-  hipStream_t copy_stream = nullptr;
-  float* pinned[2] = {nullptr, nullptr};  // bounce chunks (hipHostMalloc)
-  hipEvent_t pinned_ev[2] = {nullptr, nullptr};
-  hipEvent_t group_done[2] = {nullptr, nullptr};
+  rnamc::DevBuf<uint8_t> st_bases;
+  rnamc::DevBuf<float> st_out[2];
+  rnamc::DevBuf<float> st_logz;
+  rnamc::Stream copy_stream;     // (created by the first rnamc_bpp_batch, not with the context)
+  rnamc::PinnedBuf pinned[2];    // bounce chunks
+  rnamc::Event pinned_ev[2];
+  rnamc::Event group_done[2];
   std::vector<uint64_t> group_out_floats;  // per group, when the output is staged group-local
-  hipStream_t own_stream = nullptr;
-  hipStream_t aux_stream = nullptr;           // pair tail of large outside launches
-  std::vector<hipEvent_t> ev_a, ev_b;         // per-diagonal completion, ring of 16
+  rnamc::Stream own_stream;
+  rnamc::Stream aux_stream;  // pair tail of large outside launches
+  rnamc::EventRing ev_a{hipEventDisableTiming}, ev_b{hipEventDisableTiming};  // per-diagonal completion, ring of 16
   std::mutex mu;  // one call at a time; no entry re-enters it (StagedCall, rnamc_entries.cpp)
   // knobs
   // 0: every logsumexp fold in the reference's order (the parity gate); 1: order-free sums
@@ -99,17 +224,17 @@ struct rnamc_ctx {
   // workgroups of the previous launch (rnamc_tree.hip, Ahead)
   int64_t tree_ahead = 1;
   rnamc::TreePolicy tree_pol;  // launch shapes of the tree-order sweep ("tree_waves", "tree_short", ...)
-  hipStream_t bulk_stream = nullptr;  // k_tree_mid, beside the sweep (lowest priority)
+  rnamc::Stream bulk_stream;  // k_tree_mid, beside the sweep (lowest priority)
   // tree mode, batch form: every other group of a call sweeps on a second stream with its own half of the
   // workspace, side stream and event rings — two groups side by side fill each other's launch gaps (the
   // per-diagonal launches cost ~8 us whatever they hold); "tree_dual" 0 switches it off
   int64_t tree_dual = 1;
-  hipStream_t dual_stream = nullptr, bulk_stream2 = nullptr;
-  std::vector<hipEvent_t> ev_a2, ev_b2;
-  hipEvent_t ev_dual = nullptr;
+  hipStream_t dual_stream = nullptr, bulk_stream2 = nullptr;  // (not owned: aux_stream and own_stream)
+  rnamc::EventRing ev_a2{hipEventDisableTiming}, ev_b2{hipEventDisableTiming};
+  rnamc::Event ev_dual;
   // does bulk_stream run beside the stream of the last banded call?  (probed once per stream:
   // tree_side_stream_probe; 0 unknown, 1 yes, 2 no -> unbanded sweeps on that stream)
-  hipStream_t side_probed_for = nullptr;
+  hipStream_t side_probed_for = nullptr;  // (not owned: the caller's stream)
   bool side_probed = false;
   int side_verdict = 0;
   int64_t tree_side_force = 0;  // knob "tree_side_stream": 0 probe, 1 take it as concurrent, 2 as serialised
@@ -152,8 +277,8 @@ struct rnamc_ctx {
   rnamc_batch_stats stats{};
   std::vector<rnamc::SeqDesc> descs;       // all groups, group-major
   std::vector<uint32_t> group_begin;  // prefix into descs
-  std::vector<hipEvent_t> events;
-  std::vector<hipEvent_t> kev;        // per-launch event pairs of the outside kernels (profiling)
+  rnamc::EventRing events;            // profiling: four per group
+  rnamc::EventRing kev;               // per-launch event pairs of the outside kernels (profiling)
   std::vector<uint8_t> kev_class;     // 0 main, 1 tail, 2 / 3 small; one per pair
   // rnamc_fold_scores: sums_close key set of the last sequence it swept, so that the usual
   // "count, allocate, fill" pair of calls runs the device sweep once
@@ -162,61 +287,48 @@ struct rnamc_ctx {
   int fs_contra = -1, fs_short = -1;
   // rnamc_sample_batch (grow-only): a group's rows and log-weights, the per-wave stacks of pending
   // cells, the per-descriptor row offsets
-  uint8_t* sm_rows = nullptr;
-  float* sm_w = nullptr;
-  uint64_t* sm_stack = nullptr;
-  uint64_t* sm_rowoff = nullptr;
-  uint64_t sm_rows_cap = 0, sm_w_cap = 0, sm_stack_cap = 0, sm_rowoff_cap = 0;
+  rnamc::DevBuf<uint8_t> sm_rows;
+  rnamc::DevBuf<float> sm_w;
+  rnamc::DevBuf<uint64_t> sm_stack;
+  rnamc::DevBuf<uint64_t> sm_rowoff;
   // rnamc_mfe_batch (grow-only, beside the sampler's buffers): a group's sweep values
-  float* mf_dp = nullptr;
-  uint64_t mf_dp_cap = 0;
+  rnamc::DevBuf<float> mf_dp;
   // hard constraints of the running call: the staged words (two per base, laid out like st_bases;
   // grow-only), handed to the sweep in its SweepOpts
-  int32_t* st_cons = nullptr;
-  uint64_t st_cons_cap = 0;
+  rnamc::DevBuf<int32_t> st_cons;
   // rnamc_centroid_fold_batch (grow-only, beside the sampler's rows and stacks): a chunk's item
   // descriptors, pair counts and accuracies.  centroid_chunk_bytes: the (max,+) matrices one chunk
   // of items may take; 0 = the workspace the context holds for the group
-  rnamc::CentroidItem* cf_items = nullptr;
-  uint32_t* cf_np = nullptr;
-  float* cf_acc = nullptr;
-  uint64_t cf_items_cap = 0, cf_np_cap = 0, cf_acc_cap = 0;
+  rnamc::DevBuf<rnamc::CentroidItem> cf_items;
+  rnamc::DevBuf<uint32_t> cf_np;
+  rnamc::DevBuf<float> cf_acc;
   int64_t centroid_chunk_bytes = 0;
   // rnamc_bpp_batch_sparse (grow-only): a group's record descriptors and totals, its staged lists
   // (i, j, p) and paired probabilities
-  rnamc::SparseItem* sp_items = nullptr;
-  uint32_t* sp_totals = nullptr;
-  uint32_t* sp_i = nullptr;
-  uint32_t* sp_j = nullptr;
-  float* sp_p = nullptr;
-  float* sp_paired = nullptr;
-  uint64_t sp_items_cap = 0, sp_totals_cap = 0, sp_i_cap = 0, sp_j_cap = 0, sp_p_cap = 0, sp_paired_cap = 0;
+  rnamc::DevBuf<rnamc::SparseItem> sp_items;
+  rnamc::DevBuf<uint32_t> sp_totals, sp_i, sp_j;
+  rnamc::DevBuf<float> sp_p, sp_paired;
   // rnamc_bpp_windowed (grow-only): a chunk's window descriptors, the call's integer accumulators
   // ([d * n + i]), its band ([i * band + d]) and paired probabilities.  window_chunk_nt: nucleotides
   // of windows that go through one staged call of the sweep (never less than one window)
-  rnamc::WindowItem* wn_items = nullptr;
-  int64_t* wn_sum = nullptr;
-  uint32_t* wn_cnt = nullptr;
-  float* wn_band = nullptr;
-  float* wn_paired = nullptr;
-  uint64_t wn_items_cap = 0, wn_sum_cap = 0, wn_cnt_cap = 0, wn_band_cap = 0, wn_paired_cap = 0;
-  std::vector<hipEvent_t> wn_events;  // profiling: a pair around every run of window kernels
+  rnamc::DevBuf<rnamc::WindowItem> wn_items;
+  rnamc::DevBuf<int64_t> wn_sum;
+  rnamc::DevBuf<uint32_t> wn_cnt;
+  rnamc::DevBuf<float> wn_band, wn_paired;
+  rnamc::EventRing wn_events;  // profiling: a pair around every run of window kernels
   int64_t window_chunk_nt = 64ll << 20;
   // rnamc_mutant_scan (grow-only): the wild type's triangle and paired probabilities, kept for the
   // whole call; a chunk's descriptors for the compare and the paired kernel; the call's accumulators
   // (one sum and one max key per mutant) and a chunk's paired probabilities ([record * n + x]).
   // mutant_chunk_nt: nucleotides of mutants that go through one staged call of the sweep (never
   // less than one mutant)
-  float* mt_wt = nullptr;
-  float* mt_wt_paired = nullptr;
-  rnamc::MutantItem* mt_items = nullptr;
-  rnamc::SparseItem* mt_pitems = nullptr;
-  int64_t* mt_sum = nullptr;
-  uint64_t* mt_key = nullptr;
-  float* mt_paired = nullptr;
-  uint64_t mt_wt_cap = 0, mt_wt_paired_cap = 0, mt_items_cap = 0, mt_pitems_cap = 0, mt_sum_cap = 0, mt_key_cap = 0,
-           mt_paired_cap = 0;
-  std::vector<hipEvent_t> mt_events;  // profiling: a pair around every run of mutant kernels
+  rnamc::DevBuf<float> mt_wt, mt_wt_paired;
+  rnamc::DevBuf<rnamc::MutantItem> mt_items;
+  rnamc::DevBuf<rnamc::SparseItem> mt_pitems;
+  rnamc::DevBuf<int64_t> mt_sum;
+  rnamc::DevBuf<uint64_t> mt_key;
+  rnamc::DevBuf<float> mt_paired;
+  rnamc::EventRing mt_events;  // profiling: a pair around every run of mutant kernels
   int64_t mutant_chunk_nt = 64ll << 20;
 };
 
@@ -233,8 +345,6 @@ struct DeviceGuard {
   }
 };
 
-// Grow-only device buffer: `need` bytes at least (an eighth of headroom when it fits).
-hipError_t grow_device(void** p, uint64_t* cap, uint64_t need);
 int ensure_ws(rnamc_ctx* c, uint64_t floats);
 
 // Per-group hooks of the host-buffer entry: where group g's result goes, and what happens
@@ -261,11 +371,20 @@ struct BatchPlan {
            const std::function<uint64_t(uint32_t)>& need, const std::function<void(SeqDesc&)>& place);
   size_t n_groups() const { return c->group_begin.size() - 1; }
   uint32_t active(size_t g, uint32_t d) const;  // sequences of group g with n > d: a prefix of it
-  int create_events();                          // profiling: four per group
+  int create_events();                          // profiling: four per group (c->events)
   int finish(hipStream_t st);                   // n_groups, workspace_bytes; profiling: ms_inside / _outside / _other
 };
-// grow-only device copy of a call's descriptors (d_seqs / d_tseqs), uploaded on `st`
-int upload_descs(void** d, uint64_t* cap, const void* h, uint64_t count, uint64_t elem_bytes, hipStream_t st);
+// grow-only device copy of a call's descriptors (d_seqs / d_tseqs), uploaded on `st`: 1 024 at least, no
+// headroom; earlier calls may still read the old copy
+template <class T>
+int upload_descs(DevBuf<T>& d, const std::vector<T>& h, hipStream_t st) {
+  if (d.bytes() < h.size() * sizeof(T)) {
+    if (d) HIPCHK(hipDeviceSynchronize());
+    HIPCHK(d.replace_exact(std::max<uint64_t>(h.size(), 1024)));
+  }
+  HIPCHK(hipMemcpyAsync(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, st));
+  return RNAMC_OK;
+}
 
 int run_batch(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* d_bases, const uint64_t* offsets, bool contra,
               bool allows_short, float* d_out, const uint64_t* out_offsets, float* d_logz, hipStream_t st,

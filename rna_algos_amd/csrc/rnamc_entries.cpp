@@ -113,13 +113,11 @@ struct WalkStage {
       set_last_error(std::string(who) + ": no host memory for a group's rows");
       return RNAMC_ERR_OOM;
     }
-    HIPCHK(grow_device(reinterpret_cast<void**>(&c->sm_rows), &c->sm_rows_cap, rows_max));
-    HIPCHK(grow_device(reinterpret_cast<void**>(&c->sm_w), &c->sm_w_cap, w_max * sizeof(float)));
-    if (with_dp) HIPCHK(grow_device(reinterpret_cast<void**>(&c->mf_dp), &c->mf_dp_cap, seq_max * sizeof(float)));
-    HIPCHK(grow_device(reinterpret_cast<void**>(&c->sm_stack), &c->sm_stack_cap, stack_max * 8ull));
-    HIPCHK(grow_device(reinterpret_cast<void**>(&c->sm_rowoff), &c->sm_rowoff_cap, n_seqs * 8ull));
-    HIPCHK(hipMemcpyAsync(c->sm_rowoff, rowoff.data(), n_seqs * 8ull, hipMemcpyHostToDevice,
-                          c->own_stream));
+    HIPCHK(c->sm_rows.grow(rows_max));
+    HIPCHK(c->sm_w.grow(w_max));
+    if (with_dp) HIPCHK(c->mf_dp.grow(seq_max));
+    HIPCHK(c->sm_stack.grow(stack_max));
+    HIPCHK(c->sm_rowoff.upload(rowoff.data(), n_seqs, c->own_stream));
     return RNAMC_OK;
   }
 
@@ -179,11 +177,11 @@ int bpp_host(rnamc_ctx* c, bool locked, uint32_t n_seqs, const uint8_t* bases, c
   // thread drains them (copy stream -> pinned bounce chunks -> the caller's buffers) and
   // group g+1 sweeps into the other buffer.
   constexpr uint64_t kChunkFloats = 16ull << 20;  // 64 MB bounce chunks
-  if (!c->copy_stream) HIPCHK(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
+  if (!c->copy_stream) HIPCHK(hipStreamCreateWithFlags(c->copy_stream.put(), hipStreamNonBlocking));
   for (int k = 0; k < 2; k++) {
-    if (!c->pinned[k]) HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&c->pinned[k]), kChunkFloats * sizeof(float), hipHostMallocDefault));
-    if (!c->pinned_ev[k]) HIPCHK(hipEventCreateWithFlags(&c->pinned_ev[k], hipEventDisableTiming));
-    if (!c->group_done[k]) HIPCHK(hipEventCreateWithFlags(&c->group_done[k], hipEventDisableTiming));
+    if (!c->pinned[k]) HIPCHK(c->pinned[k].alloc(kChunkFloats));
+    if (!c->pinned_ev[k]) HIPCHK(hipEventCreateWithFlags(c->pinned_ev[k].put(), hipEventDisableTiming));
+    if (!c->group_done[k]) HIPCHK(hipEventCreateWithFlags(c->group_done[k].put(), hipEventDisableTiming));
   }
 
   // drain thread: one job per group, in order
@@ -270,15 +268,12 @@ int bpp_host(rnamc_ctx* c, bool locked, uint32_t n_seqs, const uint8_t* bases, c
       cv.wait(lk, [&] { return g < 2 || drained + 2 > g; });
       if (drain_err) return drain_err;
     }
-    const uint64_t need = std::max<uint64_t>(c->group_out_floats[g], 1) * sizeof(float);
-    if (c->st_out_cap[k] < need) {
-      // nothing on the device still writes to or reads from this buffer, but a free
-      // synchronises the device: rare (buffers only grow)
-      hipError_t e = grow_device(reinterpret_cast<void**>(&c->st_out[k]), &c->st_out_cap[k], need);
-      if (e != hipSuccess) {
-        set_last_error(std::string("result staging buffer: ") + hipGetErrorString(e));
-        return e == hipErrorOutOfMemory ? RNAMC_ERR_OOM : RNAMC_ERR_HIP;
-      }
+    // nothing on the device still writes to or reads from this buffer, but a free synchronises the
+    // device: rare (buffers only grow)
+    const hipError_t e = c->st_out[k].grow(std::max<uint64_t>(c->group_out_floats[g], 1));
+    if (e != hipSuccess) {
+      set_last_error(std::string("result staging buffer: ") + hipGetErrorString(e));
+      return e == hipErrorOutOfMemory ? RNAMC_ERR_OOM : RNAMC_ERR_HIP;
     }
     *out_base = c->st_out[k];
     return RNAMC_OK;
@@ -306,12 +301,8 @@ int bpp_host(rnamc_ctx* c, bool locked, uint32_t n_seqs, const uint8_t* bases, c
   }
   rc = sc.finish(c, rc, n_seqs, log_partition);
   if (rc) return rc;
-  for (int k = 0; k < 2; k++)
-    if (c->st_out_cap[k] > (24ull << 30)) {  // (two group buffers stay for the next call unless huge)
-      (void)hipFree(c->st_out[k]);
-      c->st_out[k] = nullptr;
-      c->st_out_cap[k] = 0;
-    }
+  for (int k = 0; k < 2; k++)  // (two group buffers stay for the next call unless huge)
+    if (c->st_out[k].bytes() > (24ull << 30)) (void)c->st_out[k].reset();
   return RNAMC_OK;
 }
 
@@ -584,26 +575,16 @@ int rnamc_durbin_batch(rnamc_ctx* c, const rnamc_align_scores* scores, uint32_t 
   if (!guard.ok) return RNAMC_ERR_NO_DEVICE;
   hipStream_t st = c->own_stream;
   const uint64_t base_lo = offsets[0], base_hi = offsets[n_seqs];
-  uint8_t* d_bases = nullptr;
-  DurbinPair* d_pairs = nullptr;
-  float* d_out = nullptr;
-  auto cleanup = [&]() {
-    (void)hipStreamSynchronize(st);
-    if (d_bases) (void)hipFree(d_bases);
-    if (d_pairs) (void)hipFree(d_pairs);
-    if (d_out) (void)hipFree(d_out);
-  };
-#define HIPCHK_D(expr)                                                     \
-  do {                                                                     \
-    hipError_t _e = (expr);                                                \
-    if (_e != hipSuccess) {                                                \
-      set_last_error(std::string(#expr) + ": " + hipGetErrorString(_e));   \
-      cleanup();                                                           \
-      return (_e == hipErrorOutOfMemory) ? RNAMC_ERR_OOM : RNAMC_ERR_HIP;  \
-    }                                                                      \
-  } while (0)
-  HIPCHK_D(hipMalloc(&d_bases, std::max<uint64_t>(base_hi - base_lo, 1)));
-  HIPCHK_D(hipMemcpyAsync(d_bases, bases + base_lo, base_hi - base_lo, hipMemcpyHostToDevice, st));
+  DevBuf<uint8_t> d_bases;
+  DevBuf<DurbinPair> d_pairs;
+  DevBuf<float> d_out;
+  // declared after the buffers, so run before they are released: whatever still uses them is done
+  struct Drain {
+    hipStream_t st;
+    ~Drain() { (void)hipStreamSynchronize(st); }
+  } drain{st};
+  HIPCHK(d_bases.replace_exact(std::max<uint64_t>(base_hi - base_lo, 1)));
+  HIPCHK(hipMemcpyAsync(d_bases, bases + base_lo, base_hi - base_lo, hipMemcpyHostToDevice, st));
   // pairs in chunks whose six matrices per pair fit the workspace budget
   const uint64_t ws_cap = static_cast<uint64_t>(std::max<int64_t>(c->group_ws_bytes, 1)) / 4;
   std::vector<DurbinPair> chunk;
@@ -613,10 +594,7 @@ int rnamc_durbin_batch(rnamc_ctx* c, const rnamc_align_scores* scores, uint32_t 
     uint64_t ws = 0, out = 0;
     uint32_t max_cells = 0, p = p0;
     for (; p < n_pairs; p++) {
-      if (pair_a[p] >= n_seqs || pair_b[p] >= n_seqs) {
-        cleanup();
-        return RNAMC_ERR_INVALID_ARG;
-      }
+      if (pair_a[p] >= n_seqs || pair_b[p] >= n_seqs) return RNAMC_ERR_INVALID_ARG;
       DurbinPair dp{};
       dp.n1 = static_cast<uint32_t>(offsets[pair_a[p] + 1] - offsets[pair_a[p]]);
       dp.n2 = static_cast<uint32_t>(offsets[pair_b[p] + 1] - offsets[pair_b[p]]);
@@ -632,39 +610,28 @@ int rnamc_durbin_batch(rnamc_ctx* c, const rnamc_align_scores* scores, uint32_t 
       out += cells;
       max_cells = static_cast<uint32_t>(std::min<uint64_t>(std::max<uint64_t>(max_cells, cells), 0xFFFFFFFFull));
     }
-    int rc = ensure_ws(c, ws);
-    if (rc) {
-      cleanup();
-      return rc;
-    }
-    if (d_pairs) HIPCHK_D(hipFree(d_pairs));
-    d_pairs = nullptr;
-    if (d_out) HIPCHK_D(hipFree(d_out));
-    d_out = nullptr;
-    HIPCHK_D(hipMalloc(&d_pairs, chunk.size() * sizeof(DurbinPair)));
-    HIPCHK_D(hipMalloc(&d_out, out * sizeof(float)));
-    HIPCHK_D(hipMemcpyAsync(d_pairs, chunk.data(), chunk.size() * sizeof(DurbinPair),
-                            hipMemcpyHostToDevice, st));
+    if (int rc = ensure_ws(c, ws)) return rc;
+    // (the chunk before is copied out: nothing uses its buffers)
+    HIPCHK(d_pairs.replace_exact(chunk.size()));
+    HIPCHK(d_out.replace_exact(out));
+    HIPCHK(hipMemcpyAsync(d_pairs, chunk.data(), chunk.size() * sizeof(DurbinPair), hipMemcpyHostToDevice, st));
     launch_durbin(d_pairs, static_cast<uint32_t>(chunk.size()), max_cells, d_bases, c->d_ws, d_out,
                   *scores, st);
-    HIPCHK_D(hipGetLastError());
+    HIPCHK(hipGetLastError());
     // one D2H per chunk, scattered on the host (a FASTA of many short records makes tens of
     // thousands of pairs: one copy each would cost more than the sweeps)
     try {
       h_out.resize(out);
     } catch (...) {
-      cleanup();
       return RNAMC_ERR_OOM;
     }
-    HIPCHK_D(hipMemcpyAsync(h_out.data(), d_out, out * sizeof(float), hipMemcpyDeviceToHost, st));
-    HIPCHK_D(hipStreamSynchronize(st));
+    HIPCHK(hipMemcpyAsync(h_out.data(), d_out, out * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
     for (size_t x = 0; x < chunk.size(); x++)
       std::memcpy(match_probs + out_offsets[p0 + x], h_out.data() + chunk[x].out_off,
                   static_cast<uint64_t>(chunk[x].n1) * chunk[x].n2 * sizeof(float));
     p0 = p;
   }
-#undef HIPCHK_D
-  cleanup();
   return RNAMC_OK;
 }
 

@@ -1,5 +1,6 @@
 // rnamc_entries.h — what the host-buffer entries share before and around their sweep: the record
-// check, the compiled constraints of a call, the staging prologue.
+// check, the compiled constraints of a call, the staging prologue, and the chunk scan of the entries
+// that put derived records of one sequence through the sweep (windows, mutants).
 #ifndef RNAMC_ENTRIES_H
 #define RNAMC_ENTRIES_H
 
@@ -86,8 +87,8 @@ struct StagedCall {
   StagedCall(rnamc_ctx* c, bool locked)
       : lock(locked ? std::unique_lock<std::mutex>() : std::unique_lock<std::mutex>(c->mu)), guard(c->device) {}
 
-  // Staging buffers live in the context and only grow (a caller that folds one record after
-  // another, like the reference's binaries, would otherwise pay hipMalloc/hipFree per call).
+  // Staging buffers are DevBufs of the context and only grow (a caller that folds one record after
+  // another, like the reference's binaries, would otherwise pay an allocation and a free per call).
   int stage(rnamc_ctx* c, const char* who, uint32_t n_seqs, const uint8_t* bases, const uint64_t* offsets,
             const ConsCall& cons, bool with_logz = true) {
     if (!guard.ok) return RNAMC_ERR_NO_DEVICE;
@@ -100,16 +101,12 @@ struct StagedCall {
     const uint64_t base_lo = offsets[0], base_hi = offsets[n_seqs];
     for (uint32_t s = 0; s <= n_seqs; s++) doff[s] = offsets[s] - base_lo;
     HIPCHK(hipStreamSynchronize(c->own_stream));
-    HIPCHK(grow_device(reinterpret_cast<void**>(&c->st_bases), &c->st_bases_cap, base_hi - base_lo));
-    if (with_logz)
-      HIPCHK(grow_device(reinterpret_cast<void**>(&c->st_logz), &c->st_logz_cap,
-                         static_cast<uint64_t>(n_seqs) * sizeof(float)));
+    HIPCHK(c->st_bases.grow(base_hi - base_lo));
+    if (with_logz) HIPCHK(c->st_logz.grow(n_seqs));
     HIPCHK(hipMemcpyAsync(c->st_bases, bases + base_lo, base_hi - base_lo, hipMemcpyHostToDevice,
                           c->own_stream));
     if (!cons.active) return RNAMC_OK;
-    HIPCHK(grow_device(reinterpret_cast<void**>(&c->st_cons), &c->st_cons_cap, cons.words.size() * sizeof(int32_t)));
-    HIPCHK(hipMemcpyAsync(c->st_cons, cons.words.data(), cons.words.size() * sizeof(int32_t), hipMemcpyHostToDevice,
-                          c->own_stream));
+    HIPCHK(c->st_cons.upload(cons.words.data(), cons.words.size(), c->own_stream));
     opts.cons = c->st_cons;
     opts.max_span = cons.max_span;
     return RNAMC_OK;
@@ -132,8 +129,7 @@ struct StagedCall {
 // before-hook of the entries that take no triangles to the host: the finalize kernel writes the
 // group's triangles somewhere, at group-local offsets -- one device buffer for all groups
 inline int group_triangles(rnamc_ctx* c, size_t g, float** out_base) {
-  const uint64_t need = std::max<uint64_t>(c->group_out_floats[g], 1) * sizeof(float);
-  HIPCHK(grow_device(reinterpret_cast<void**>(&c->st_out[0]), &c->st_out_cap[0], need));
+  HIPCHK(c->st_out[0].grow(std::max<uint64_t>(c->group_out_floats[g], 1)));
   *out_base = c->st_out[0];
   return RNAMC_OK;
 }
@@ -158,21 +154,105 @@ inline void add_sweep_stats(rnamc_batch_stats* to, const rnamc_batch_stats& s) {
   to->tree_side_stream = s.tree_side_stream;
 }
 
-// profiling: event pairs around an entry's own kernels (pair p = events 2p, 2p + 1 of a grow-only
-// ring of the context), read once their stream is drained
-inline int event_pairs(std::vector<hipEvent_t>* ring, size_t pairs) {
-  while (ring->size() < 2 * pairs) {
-    hipEvent_t e;
-    HIPCHK(hipEventCreate(&e));
-    ring->push_back(e);
-  }
+// The end of one staged call of an entry that runs the sweep several times: its own launches and the
+// milliseconds of its event pairs (EventRing::pairs) into the two statistics fields that are the
+// entry's, then the call's statistics added to `total`.
+inline int fold_call_stats(rnamc_ctx* c, rnamc_batch_stats* total, uint64_t launches, const EventRing& ring,
+                           size_t ev_pairs, uint64_t rnamc_batch_stats::*launches_own,
+                           double rnamc_batch_stats::*ms_own) {
+  c->stats.launches_other += launches;
+  c->stats.*launches_own = launches;
+  c->stats.*ms_own = 0.0;
+  if (c->profile != 0) HIPCHK(ring.pairs_ms(ev_pairs, &(c->stats.*ms_own)));
+  add_sweep_stats(total, c->stats);
+  total->*launches_own += c->stats.*launches_own;
+  total->*ms_own += c->stats.*ms_own;
   return RNAMC_OK;
 }
-inline int event_pairs_ms(const std::vector<hipEvent_t>& ring, size_t pairs, double* ms) {
-  for (size_t p = 0; p < pairs; p++) {
-    float t = 0.f;
-    HIPCHK(hipEventElapsedTime(&t, ring[2 * p], ring[2 * p + 1]));
-    *ms += t;
+
+// One chunk scan: `count` derived records of one fixed length, cut out of one sequence, through the
+// bpp sweep chunk by chunk (`per_chunk` records a staged call) and group by group.  A group's
+// triangles stay on the device (st_out[0], group-local offsets) and the caller's kernels run behind
+// its finalize kernel in stream order, without a host round-trip.  The caller says how a record is
+// cut, what an item holds, which kernels a slice of descriptors launches and which statistics
+// fields are its own; the scan owns everything else.
+struct ChunkScan {
+  const char* who;   // the entry's name, and the noun of its records ("windows") for the messages
+  const char* what;
+  uint32_t rec_len;
+  uint64_t count, per_chunk;
+  bool with_constraint;
+  uint32_t max_bp_span;
+  bool contra, allows_short;
+  float* log_partition;  // of record 0 of the scan, or null
+  EventRing* events;     // profiling: a pair around every group's launches
+  uint64_t rnamc_batch_stats::*launches_own;
+  double rnamc_batch_stats::*ms_own;
+  // record x of the scan (and its constraint, where there is one) written to rec / cons
+  std::function<void(uint64_t x, uint8_t* rec, char* cons)> cut;
+  // the chunk starting at record x0 is planned (c->descs, m of them): fill and upload its items
+  std::function<int(uint64_t x0, uint32_t m)> upload_items;
+  // the kernels of descriptors [first_desc, first_desc + k), k <= 65 535 -> the number of launches
+  std::function<uint64_t(uint32_t first_desc, uint32_t k)> launch;
+  // optional: after the chunk's sweep is enqueued, before its stream is drained
+  std::function<int(uint64_t x0, uint32_t m)> after_sweep;
+};
+
+inline int scan_chunks(rnamc_ctx* c, const ChunkScan& s, rnamc_batch_stats* total) {
+  hipStream_t st = c->own_stream;  // (a call with hooks never takes the two-stream route of the tree order)
+  const uint32_t w = s.rec_len;
+  std::vector<uint8_t> cb;
+  std::vector<char> cc;
+  std::vector<uint64_t> offs;
+  try {  // nothing may throw across the C boundary
+    cb.resize(s.per_chunk * w);
+    if (s.with_constraint) cc.resize(s.per_chunk * w);
+    offs.resize(s.per_chunk + 1);
+  } catch (const std::exception&) {
+    set_last_error(std::string(s.who) + ": no host memory for a chunk of " + s.what);
+    return RNAMC_ERR_OOM;
+  }
+  const bool prof = c->profile != 0;
+  for (uint64_t x0 = 0; x0 < s.count; x0 += s.per_chunk) {
+    const uint32_t m = static_cast<uint32_t>(std::min<uint64_t>(s.per_chunk, s.count - x0));
+    // the chunk's records as ordinary records (they may overlap in the sequence; the record checks
+    // want monotone offsets)
+    for (uint32_t x = 0; x <= m; x++) offs[x] = static_cast<uint64_t>(x) * w;
+    for (uint32_t x = 0; x < m; x++)
+      s.cut(x0 + x, cb.data() + offs[x], s.with_constraint ? cc.data() + offs[x] : nullptr);
+    ConsCall cons;
+    if (int rc = cons.prepare(m, offs.data(), s.with_constraint ? cc.data() : nullptr, s.max_bp_span)) return rc;
+    StagedCall sc(c, true);
+    if (int rc = sc.stage(c, s.who, m, cb.data(), offs.data(), cons)) return rc;
+    uint64_t launches = 0;  // (run_batch* resets the context's statistics when it starts)
+    size_t ev_pairs = 0;
+    GroupHooks hooks;
+    hooks.before = [&](size_t g, float** out_base) -> int {
+      if (g == 0) {
+        // the plan of the chunk is cut: one item per record for all its groups, uploaded once
+        if (int rc = s.upload_items(x0, m)) return rc;
+        if (prof) HIPCHK(s.events->pairs(c->group_begin.size() - 1));
+      }
+      return group_triangles(c, g, out_base);
+    };
+    hooks.after = [&](size_t g, uint32_t first_desc, uint32_t n_desc) -> int {
+      // the group's finalize kernel is enqueued on `st`; the next group's writes st_out[0] behind
+      // these launches in stream order
+      if (prof) HIPCHK(hipEventRecord((*s.events)[2 * g], st));
+      for (uint32_t x = 0; x < n_desc; x += 65535u) launches += s.launch(first_desc + x, std::min(n_desc - x, 65535u));
+      HIPCHK(hipGetLastError());
+      if (prof) {
+        HIPCHK(hipEventRecord((*s.events)[2 * g + 1], st));
+        ev_pairs = g + 1;
+      }
+      return RNAMC_OK;
+    };
+    int rc = run_batch_mode(c, m, c->st_bases, sc.doff.data(), s.contra, s.allows_short, nullptr, nullptr,
+                            c->st_logz, st, sc.opts, &hooks);
+    if (rc == RNAMC_OK && s.after_sweep) rc = s.after_sweep(x0, m);
+    rc = sc.finish(c, rc, m, s.log_partition ? s.log_partition + x0 : nullptr);
+    if (rc) return rc;
+    if (int rc2 = fold_call_stats(c, total, launches, *s.events, ev_pairs, s.launches_own, s.ms_own)) return rc2;
   }
   return RNAMC_OK;
 }

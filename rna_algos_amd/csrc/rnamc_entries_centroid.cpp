@@ -145,9 +145,8 @@ int centroid_fold_batch_core(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* bases
       set_last_error("rnamc_centroid_fold_batch: no host memory for a group");
       return RNAMC_ERR_OOM;
     }
-    HIPCHK(grow_device(reinterpret_cast<void**>(&c->cf_items), &c->cf_items_cap, count * sizeof(CentroidItem)));
-    HIPCHK(grow_device(reinterpret_cast<void**>(&c->cf_acc), &c->cf_acc_cap, count * sizeof(float)));
-    HIPCHK(hipMemcpyAsync(c->cf_items, items.data(), count * sizeof(CentroidItem), hipMemcpyHostToDevice, st));
+    HIPCHK(c->cf_acc.grow(count));
+    HIPCHK(c->cf_items.upload(items.data(), count, st));
     launch_centroid_pmax(c->cf_items, c->st_out[0], c->cf_acc, count, st);
     launches++;
     HIPCHK(hipGetLastError());
@@ -213,13 +212,11 @@ int centroid_fold_batch_core(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* bases
       const uint32_t cmax = items[0].n;
       const uint64_t row_bytes = h_rows.size();
       const uint32_t waves = waves_of(cus, ni, cmax);
-      HIPCHK(grow_device(reinterpret_cast<void**>(&c->cf_items), &c->cf_items_cap, ni * sizeof(CentroidItem)));
-      HIPCHK(grow_device(reinterpret_cast<void**>(&c->cf_np), &c->cf_np_cap, ni * sizeof(uint32_t)));
-      HIPCHK(grow_device(reinterpret_cast<void**>(&c->cf_acc), &c->cf_acc_cap, ni * sizeof(float)));
-      HIPCHK(grow_device(reinterpret_cast<void**>(&c->sm_rows), &c->sm_rows_cap, row_bytes));
-      HIPCHK(grow_device(reinterpret_cast<void**>(&c->sm_stack), &c->sm_stack_cap,
-                         static_cast<uint64_t>(waves) * (cmax + 1ull) * 8ull));
-      HIPCHK(hipMemcpyAsync(c->cf_items, items.data(), ni * sizeof(CentroidItem), hipMemcpyHostToDevice, st));
+      HIPCHK(c->cf_np.grow(ni));
+      HIPCHK(c->cf_acc.grow(ni));
+      HIPCHK(c->sm_rows.grow(row_bytes));
+      HIPCHK(c->sm_stack.grow(static_cast<uint64_t>(waves) * (cmax + 1ull)));
+      HIPCHK(c->cf_items.upload(items.data(), ni, st));
       CentroidChunk a{};
       a.items = c->cf_items;
       a.bpp = c->st_out[0];

@@ -82,22 +82,6 @@ int mutant_scan_core(rnamc_ctx* c, const uint8_t* bases, uint32_t n, const char*
   const bool prof = c->profile != 0;
   const bool wants_paired = paired_prob != nullptr && count != 0;
   rnamc_batch_stats total{};
-  uint64_t launches = 0;  // (run_batch* resets the context's statistics when it starts)
-  size_t ev_pairs = 0;
-  // the end of one staged call: the statistics of its sweep and of the kernels behind it
-  auto account = [&]() -> int {
-    c->stats.launches_other += launches;
-    c->stats.launches_mutant = launches;
-    c->stats.ms_mutant = 0.0;
-    if (prof)
-      if (int rc = event_pairs_ms(c->mt_events, ev_pairs, &c->stats.ms_mutant)) return rc;
-    add_sweep_stats(&total, c->stats);
-    total.launches_mutant += c->stats.launches_mutant;
-    total.ms_mutant += c->stats.ms_mutant;
-    launches = 0;
-    ev_pairs = 0;
-    return RNAMC_OK;
-  };
 
   // ---- the wild type: a call of one record, its triangle parked where no later group writes ----
   {
@@ -107,19 +91,20 @@ int mutant_scan_core(rnamc_ctx* c, const uint8_t* bases, uint32_t n, const char*
     StagedCall sc(c, true);
     if (int rc = sc.stage(c, "rnamc_mutant_scan", 1, bases, offs, cons)) return rc;
     const SparseItem wt_item = paired_item(0, 0, n);  // (lives until sc.finish has drained the stream)
+    uint64_t launches = 0;  // (run_batch* resets the context's statistics when it starts)
+    size_t ev_pairs = 0;
     GroupHooks hooks;
     hooks.before = [&](size_t, float** out_base) -> int {
-      HIPCHK(grow_device(reinterpret_cast<void**>(&c->mt_wt), &c->mt_wt_cap, len * sizeof(float)));
+      HIPCHK(c->mt_wt.grow(len));
       *out_base = c->mt_wt;
       return RNAMC_OK;
     };
     hooks.after = [&](size_t, uint32_t, uint32_t) -> int {
       if (!wt_paired_prob) return RNAMC_OK;
-      HIPCHK(grow_device(reinterpret_cast<void**>(&c->mt_wt_paired), &c->mt_wt_paired_cap, n * sizeof(float)));
-      HIPCHK(grow_device(reinterpret_cast<void**>(&c->mt_pitems), &c->mt_pitems_cap, sizeof(SparseItem)));
-      HIPCHK(hipMemcpyAsync(c->mt_pitems, &wt_item, sizeof(SparseItem), hipMemcpyHostToDevice, st));
+      HIPCHK(c->mt_wt_paired.grow(n));
+      HIPCHK(c->mt_pitems.upload(&wt_item, 1, st));
       if (prof) {
-        if (int rc = event_pairs(&c->mt_events, 1)) return rc;
+        HIPCHK(c->mt_events.pairs(1));
         HIPCHK(hipEventRecord(c->mt_events[0], st));
       }
       launch_sparse_paired(c->mt_pitems, 1, n, c->mt_wt, c->mt_wt_paired, st);
@@ -136,7 +121,9 @@ int mutant_scan_core(rnamc_ctx* c, const uint8_t* bases, uint32_t n, const char*
                             nullptr, nullptr, c->st_logz, st, sc.opts, &hooks);
     rc = sc.finish(c, rc, 1, wt_log_partition);
     if (rc) return rc;
-    if (int rc2 = account()) return rc2;
+    if (int rc2 = fold_call_stats(c, &total, launches, c->mt_events, ev_pairs, &rnamc_batch_stats::launches_mutant,
+                                  &rnamc_batch_stats::ms_mutant))
+      return rc2;
   }
   if (count == 0) {
     c->stats = total;
@@ -144,110 +131,73 @@ int mutant_scan_core(rnamc_ctx* c, const uint8_t* bases, uint32_t n, const char*
   }
 
   // ---- the mutants ----
-  HIPCHK(grow_device(reinterpret_cast<void**>(&c->mt_sum), &c->mt_sum_cap, count * sizeof(int64_t)));
-  HIPCHK(grow_device(reinterpret_cast<void**>(&c->mt_key), &c->mt_key_cap, count * sizeof(uint64_t)));
+  HIPCHK(c->mt_sum.grow(count));
+  HIPCHK(c->mt_key.grow(count));
   // once per call, not per chunk
   HIPCHK(hipMemsetAsync(c->mt_sum, 0, count * sizeof(int64_t), st));
   HIPCHK(hipMemsetAsync(c->mt_key, 0, count * sizeof(uint64_t), st));
+  ChunkScan s{};
+  s.who = "rnamc_mutant_scan";
+  s.what = "mutants";
+  s.rec_len = n;
+  s.count = count;
   // mutants of a chunk: mutant_chunk_nt nucleotides, one mutant at least
-  const uint64_t per_chunk =
-      std::min<uint64_t>(std::max<uint64_t>(static_cast<uint64_t>(c->mutant_chunk_nt) / n, 1), count);
-  std::vector<uint8_t> cb;
-  std::vector<char> cc;
-  std::vector<uint64_t> offs, h_key;
-  std::vector<MutantItem> items;
+  s.per_chunk = std::min<uint64_t>(std::max<uint64_t>(static_cast<uint64_t>(c->mutant_chunk_nt) / n, 1), count);
+  s.with_constraint = constraint != nullptr;
+  s.max_bp_span = max_bp_span;
+  s.contra = uses_contra_model != 0;
+  s.allows_short = allows_short_hairpins != 0;
+  s.log_partition = log_partition + first;
+  s.events = &c->mt_events;
+  s.launches_own = &rnamc_batch_stats::launches_mutant;
+  s.ms_own = &rnamc_batch_stats::ms_mutant;
+  std::vector<uint64_t> h_key;
+  std::vector<MutantItem> items;  // (the host copies live until the chunk's stream is drained)
   std::vector<SparseItem> pitems;
   try {  // nothing may throw across the C boundary
-    cb.resize(per_chunk * n);
-    if (constraint) cc.resize(per_chunk * n);
-    offs.resize(per_chunk + 1);
-    items.resize(per_chunk);
-    if (wants_paired) pitems.resize(per_chunk);
+    items.resize(s.per_chunk);
+    if (wants_paired) pitems.resize(s.per_chunk);
     if (max_dp || max_i || max_j) h_key.resize(count);
   } catch (const std::exception&) {
     set_last_error("rnamc_mutant_scan: no host memory for a chunk of mutants");
     return RNAMC_ERR_OOM;
   }
-  if (wants_paired)
-    HIPCHK(grow_device(reinterpret_cast<void**>(&c->mt_paired), &c->mt_paired_cap,
-                       per_chunk * n * sizeof(float)));
-  for (uint64_t x0 = 0; x0 < count; x0 += per_chunk) {
-    const uint32_t m = static_cast<uint32_t>(std::min<uint64_t>(per_chunk, count - x0));
-    // the chunk's mutants as ordinary records: the wild type with one byte changed
-    for (uint32_t x = 0; x < m; x++) {
-      const uint64_t mu = first + x0 + x, idx = mu / 3;
-      const uint32_t pos = positions ? positions[idx] : static_cast<uint32_t>(idx);
-      uint8_t* rec = cb.data() + static_cast<uint64_t>(x) * n;
-      std::memcpy(rec, bases, n);
-      rec[pos] = mutant_base_of(bases[pos], static_cast<uint32_t>(mu % 3));
-      if (constraint) std::memcpy(cc.data() + static_cast<uint64_t>(x) * n, constraint, n);
-      offs[x] = static_cast<uint64_t>(x) * n;
+  if (wants_paired) HIPCHK(c->mt_paired.grow(s.per_chunk * n));
+  // a mutant as an ordinary record: the wild type with one byte changed
+  s.cut = [&](uint64_t x, uint8_t* rec, char* cons) {
+    const uint64_t mu = first + x, idx = mu / 3;
+    const uint32_t pos = positions ? positions[idx] : static_cast<uint32_t>(idx);
+    std::memcpy(rec, bases, n);
+    rec[pos] = mutant_base_of(bases[pos], static_cast<uint32_t>(mu % 3));
+    if (cons) std::memcpy(cons, constraint, n);
+  };
+  s.upload_items = [&](uint64_t x0, uint32_t m) -> int {
+    for (size_t x = 0; x < c->descs.size(); x++) {
+      const SeqDesc& sd = c->descs[x];
+      items[x].bpp_off = sd.out_off;
+      items[x].slot = x0 + sd.batch_idx;
+      if (wants_paired) pitems[x] = paired_item(sd.out_off, static_cast<uint64_t>(sd.batch_idx) * n, n);
     }
-    offs[m] = static_cast<uint64_t>(m) * n;
-    ConsCall cons;
-    if (int rc = cons.prepare(m, offs.data(), constraint ? cc.data() : nullptr, max_bp_span)) return rc;
-    StagedCall sc(c, true);
-    if (int rc = sc.stage(c, "rnamc_mutant_scan", m, cb.data(), offs.data(), cons)) return rc;
-    GroupHooks hooks;
-    // (the group's triangles stay on the device, at group-local offsets)
-    hooks.before = [&](size_t g, float** out_base) -> int {
-      if (g == 0) {
-        // the plan of the chunk is cut: one item per record for all its groups, uploaded once (the
-        // host copies live until the chunk's stream is drained)
-        for (size_t x = 0; x < c->descs.size(); x++) {
-          const SeqDesc& sd = c->descs[x];
-          items[x].bpp_off = sd.out_off;
-          items[x].slot = x0 + sd.batch_idx;
-          if (wants_paired) pitems[x] = paired_item(sd.out_off, static_cast<uint64_t>(sd.batch_idx) * n, n);
-        }
-        HIPCHK(grow_device(reinterpret_cast<void**>(&c->mt_items), &c->mt_items_cap,
-                           static_cast<uint64_t>(m) * sizeof(MutantItem)));
-        HIPCHK(hipMemcpyAsync(c->mt_items, items.data(), static_cast<uint64_t>(m) * sizeof(MutantItem),
-                              hipMemcpyHostToDevice, st));
-        if (wants_paired) {
-          HIPCHK(grow_device(reinterpret_cast<void**>(&c->mt_pitems), &c->mt_pitems_cap,
-                             static_cast<uint64_t>(m) * sizeof(SparseItem)));
-          HIPCHK(hipMemcpyAsync(c->mt_pitems, pitems.data(), static_cast<uint64_t>(m) * sizeof(SparseItem),
-                                hipMemcpyHostToDevice, st));
-        }
-        if (prof)
-          if (int rc = event_pairs(&c->mt_events, c->group_begin.size() - 1)) return rc;
-      }
-      return group_triangles(c, g, out_base);
-    };
-    hooks.after = [&](size_t g, uint32_t first_desc, uint32_t n_desc) -> int {
-      // the group's finalize kernel is enqueued on `st`; the next group's writes st_out[0] behind
-      // these launches in stream order: no host round-trip
-      if (prof) HIPCHK(hipEventRecord(c->mt_events[2 * g], st));
-      for (uint32_t x = 0; x < n_desc; x += 65535u) {
-        const uint32_t k = std::min(n_desc - x, 65535u);
-        launch_mutant_compare(c->mt_items + first_desc + x, k, c->mt_wt, c->st_out[0], n, c->mt_sum, c->mt_key, st);
-        launches++;
-        if (wants_paired) {
-          launch_sparse_paired(c->mt_pitems + first_desc + x, k, n, c->st_out[0], c->mt_paired, st);
-          launches++;
-        }
-      }
-      HIPCHK(hipGetLastError());
-      if (prof) {
-        HIPCHK(hipEventRecord(c->mt_events[2 * g + 1], st));
-        ev_pairs = g + 1;
-      }
-      return RNAMC_OK;
-    };
-    int rc = run_batch_mode(c, m, c->st_bases, sc.doff.data(), uses_contra_model != 0, allows_short_hairpins != 0,
-                            nullptr, nullptr, c->st_logz, st, sc.opts, &hooks);
-    if (rc == RNAMC_OK && wants_paired)
+    HIPCHK(c->mt_items.upload(items.data(), m, st));
+    if (wants_paired) HIPCHK(c->mt_pitems.upload(pitems.data(), m, st));
+    return RNAMC_OK;
+  };
+  s.launch = [&](uint32_t first_desc, uint32_t k) -> uint64_t {
+    launch_mutant_compare(c->mt_items + first_desc, k, c->mt_wt, c->st_out[0], n, c->mt_sum, c->mt_key, st);
+    if (!wants_paired) return 1;
+    launch_sparse_paired(c->mt_pitems + first_desc, k, n, c->st_out[0], c->mt_paired, st);
+    return 2;
+  };
+  if (wants_paired)
+    s.after_sweep = [&](uint64_t x0, uint32_t m) -> int {
       if (hipMemcpyAsync(paired_prob + (first + x0) * n, c->mt_paired, static_cast<uint64_t>(m) * n * sizeof(float),
-                         hipMemcpyDeviceToHost, st) != hipSuccess) {
-        set_last_error("rnamc_mutant_scan: copying a chunk's paired probabilities failed");
-        (void)hipGetLastError();
-        rc = RNAMC_ERR_HIP;
-      }
-    rc = sc.finish(c, rc, m, log_partition + first + x0);
-    if (rc) return rc;
-    if (int rc2 = account()) return rc2;
-  }
+                         hipMemcpyDeviceToHost, st) == hipSuccess)
+        return RNAMC_OK;
+      set_last_error("rnamc_mutant_scan: copying a chunk's paired probabilities failed");
+      (void)hipGetLastError();
+      return RNAMC_ERR_HIP;
+    };
+  if (int rc = scan_chunks(c, s, &total)) return rc;
   c->stats = total;
   // the accumulators, after the last chunk
   if (pair_dist2_q)

@@ -83,10 +83,9 @@ int bpp_batch_sparse_core(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* bases, c
       set_last_error("rnamc_bpp_batch_sparse: the workspace cannot hold the block counts");
       return RNAMC_ERR_HIP;
     }
-    uint32_t* d_blocks = reinterpret_cast<uint32_t*>(c->d_ws);
-    HIPCHK(grow_device(reinterpret_cast<void**>(&c->sp_items), &c->sp_items_cap, count * sizeof(SparseItem)));
-    HIPCHK(grow_device(reinterpret_cast<void**>(&c->sp_totals), &c->sp_totals_cap, count * sizeof(uint32_t)));
-    HIPCHK(hipMemcpyAsync(c->sp_items, items.data(), count * sizeof(SparseItem), hipMemcpyHostToDevice, st));
+    uint32_t* d_blocks = reinterpret_cast<uint32_t*>(c->d_ws.get());
+    HIPCHK(c->sp_totals.grow(count));
+    HIPCHK(c->sp_items.upload(items.data(), count, st));
     // records longest first: the first item of a launch has the most blocks
     for (uint32_t x = 0; x < count; x += 65535u) {
       launch_sparse_count(c->sp_items + x, std::min(count - x, 65535u), items[x].n_blocks, c->st_out[0], d_blocks,
@@ -111,9 +110,9 @@ int bpp_batch_sparse_core(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* bases, c
       if (fill) pair_start[r] = start + items[x].out_off;
     }
     if (fill && group_total) {
-      HIPCHK(grow_device(reinterpret_cast<void**>(&c->sp_i), &c->sp_i_cap, group_total * sizeof(uint32_t)));
-      HIPCHK(grow_device(reinterpret_cast<void**>(&c->sp_j), &c->sp_j_cap, group_total * sizeof(uint32_t)));
-      HIPCHK(grow_device(reinterpret_cast<void**>(&c->sp_p), &c->sp_p_cap, group_total * sizeof(float)));
+      HIPCHK(c->sp_i.grow(group_total));
+      HIPCHK(c->sp_j.grow(group_total));
+      HIPCHK(c->sp_p.grow(group_total));
       HIPCHK(hipMemcpyAsync(c->sp_items, items.data(), count * sizeof(SparseItem), hipMemcpyHostToDevice, st));
       for (uint32_t x = 0; x < count; x += 65535u) {
         launch_sparse_fill(c->sp_items + x, std::min(count - x, 65535u), items[x].n_blocks, c->st_out[0], d_blocks,
@@ -127,7 +126,7 @@ int bpp_batch_sparse_core(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* bases, c
       HIPCHK(hipMemcpyAsync(pair_prob + start, c->sp_p, group_total * sizeof(float), hipMemcpyDeviceToHost, st));
     }
     if (paired_prob) {
-      HIPCHK(grow_device(reinterpret_cast<void**>(&c->sp_paired), &c->sp_paired_cap, nt * sizeof(float)));
+      HIPCHK(c->sp_paired.grow(nt));
       for (uint32_t x = 0; x < count; x += 65535u) {
         launch_sparse_paired(c->sp_items + x, std::min(count - x, 65535u), items[x].n, c->st_out[0], c->sp_paired,
                              st);

@@ -71,8 +71,8 @@ int bpp_windowed_accumulate(rnamc_ctx* c, const WindowPlan& wp, const uint8_t* b
   const uint64_t cells = static_cast<uint64_t>(wp.band) * wp.n;
   const uint32_t w = wp.w;
   HIPCHK(hipStreamSynchronize(st));
-  HIPCHK(grow_device(reinterpret_cast<void**>(&c->wn_sum), &c->wn_sum_cap, cells * sizeof(int64_t)));
-  HIPCHK(grow_device(reinterpret_cast<void**>(&c->wn_cnt), &c->wn_cnt_cap, cells * sizeof(uint32_t)));
+  HIPCHK(c->wn_sum.grow(cells));
+  HIPCHK(c->wn_cnt.grow(cells));
   // once per call, not per chunk
   HIPCHK(hipMemsetAsync(c->wn_sum, 0, cells * sizeof(int64_t), st));
   HIPCHK(hipMemsetAsync(c->wn_cnt, 0, cells * sizeof(uint32_t), st));
@@ -81,87 +81,48 @@ int bpp_windowed_accumulate(rnamc_ctx* c, const WindowPlan& wp, const uint8_t* b
     c->stats = total;
     return RNAMC_OK;
   }
+  ChunkScan s{};
+  s.who = "rnamc_bpp_windowed";
+  s.what = "windows";
+  s.rec_len = w;
+  s.count = count;
   // windows of a chunk: window_chunk_nt nucleotides, one window at least, a u32 of records at most
-  const uint64_t per_chunk = std::min<uint64_t>(
+  s.per_chunk = std::min<uint64_t>(
       std::min<uint64_t>(std::max<uint64_t>(static_cast<uint64_t>(c->window_chunk_nt) / w, 1), count), 0xffffffffull);
-  std::vector<uint8_t> cb;
-  std::vector<char> cc;
-  std::vector<uint64_t> offs;
-  std::vector<WindowItem> items;
+  s.with_constraint = constraint != nullptr;
+  s.max_bp_span = wp.band;
+  s.contra = uses_contra_model != 0;
+  s.allows_short = allows_short_hairpins != 0;
+  s.log_partition = window_log_partition ? window_log_partition + first : nullptr;
+  s.events = &c->wn_events;
+  s.launches_own = &rnamc_batch_stats::launches_window;
+  s.ms_own = &rnamc_batch_stats::ms_window;
+  std::vector<WindowItem> items;  // (the host copy lives until the chunk's stream is drained)
   try {  // nothing may throw across the C boundary
-    cb.resize(per_chunk * w);
-    if (constraint) cc.resize(per_chunk * w);
-    offs.resize(per_chunk + 1);
-    items.resize(per_chunk);
+    items.resize(s.per_chunk);
   } catch (const std::exception&) {
     set_last_error("rnamc_bpp_windowed: no host memory for a chunk of windows");
     return RNAMC_ERR_OOM;
   }
-  const bool prof = c->profile != 0;
-  for (uint64_t x0 = 0; x0 < count; x0 += per_chunk) {
-    const uint32_t m = static_cast<uint32_t>(std::min<uint64_t>(per_chunk, count - x0));
-    // the chunk's windows as ordinary records (windows overlap; the record checks want monotone offsets)
-    for (uint32_t x = 0; x < m; x++) {
-      const uint64_t s = wp.start(first + x0 + x);
-      std::memcpy(cb.data() + static_cast<uint64_t>(x) * w, bases + s, w);
-      if (constraint) std::memcpy(cc.data() + static_cast<uint64_t>(x) * w, constraint + s, w);
-      offs[x] = static_cast<uint64_t>(x) * w;
+  s.cut = [&](uint64_t x, uint8_t* rec, char* cons) {
+    const uint64_t at = wp.start(first + x);
+    std::memcpy(rec, bases + at, w);
+    if (cons) std::memcpy(cons, constraint + at, w);
+  };
+  s.upload_items = [&](uint64_t x0, uint32_t m) -> int {
+    for (size_t x = 0; x < c->descs.size(); x++) {
+      const SeqDesc& sd = c->descs[x];
+      items[x].bpp_off = sd.out_off;
+      items[x].start = wp.start(first + x0 + sd.batch_idx);
     }
-    offs[m] = static_cast<uint64_t>(m) * w;
-    ConsCall cons;
-    if (int rc = cons.prepare(m, offs.data(), constraint ? cc.data() : nullptr, wp.band)) return rc;
-    StagedCall sc(c, true);
-    if (int rc = sc.stage(c, "rnamc_bpp_windowed", m, cb.data(), offs.data(), cons)) return rc;
-    uint64_t launches = 0;  // (run_batch* resets the context's statistics when it starts)
-    size_t ev_pairs = 0;
-    GroupHooks hooks;
-    // (the group's triangles stay on the device, at group-local offsets)
-    hooks.before = [&](size_t g, float** out_base) -> int {
-      if (g == 0) {
-        // the plan of the chunk is cut: one item per record for all its groups, uploaded once (the
-        // host copy lives until the chunk's stream is drained)
-        for (size_t x = 0; x < c->descs.size(); x++) {
-          const SeqDesc& sd = c->descs[x];
-          items[x].bpp_off = sd.out_off;
-          items[x].start = wp.start(first + x0 + sd.batch_idx);
-        }
-        HIPCHK(grow_device(reinterpret_cast<void**>(&c->wn_items), &c->wn_items_cap,
-                           static_cast<uint64_t>(m) * sizeof(WindowItem)));
-        HIPCHK(hipMemcpyAsync(c->wn_items, items.data(), static_cast<uint64_t>(m) * sizeof(WindowItem),
-                              hipMemcpyHostToDevice, st));
-        if (prof)
-          if (int rc = event_pairs(&c->wn_events, c->group_begin.size() - 1)) return rc;
-      }
-      return group_triangles(c, g, out_base);
-    };
-    hooks.after = [&](size_t g, uint32_t first_desc, uint32_t n_desc) -> int {
-      // the group's finalize kernel is enqueued on `st`; the next group's writes st_out[0] behind
-      // these launches in stream order: no host round-trip
-      if (prof) HIPCHK(hipEventRecord(c->wn_events[2 * g], st));
-      for (uint32_t x = 0; x < n_desc; x += 65535u) {
-        launch_window_accumulate(c->wn_items + first_desc + x, std::min(n_desc - x, 65535u), c->st_out[0], w,
-                                 wp.band, wp.n, c->wn_sum, c->wn_cnt, st);
-        launches++;
-      }
-      HIPCHK(hipGetLastError());
-      if (prof) {
-        HIPCHK(hipEventRecord(c->wn_events[2 * g + 1], st));
-        ev_pairs = g + 1;
-      }
-      return RNAMC_OK;
-    };
-    int rc = run_batch_mode(c, m, c->st_bases, sc.doff.data(), uses_contra_model != 0, allows_short_hairpins != 0,
-                            nullptr, nullptr, c->st_logz, st, sc.opts, &hooks);
-    c->stats.launches_other += launches;
-    c->stats.launches_window += launches;
-    rc = sc.finish(c, rc, m, window_log_partition ? window_log_partition + first + x0 : nullptr);
-    if (rc) return rc;
-    if (prof)
-      if (int rc2 = event_pairs_ms(c->wn_events, ev_pairs, &c->stats.ms_window)) return rc2;
-    add_sweep_stats(&total, c->stats);
-    total.launches_window += c->stats.launches_window;
-    total.ms_window += c->stats.ms_window;
-  }
+    HIPCHK(c->wn_items.upload(items.data(), m, st));
+    return RNAMC_OK;
+  };
+  s.launch = [&](uint32_t first_desc, uint32_t k) -> uint64_t {
+    launch_window_accumulate(c->wn_items + first_desc, k, c->st_out[0], w, wp.band, wp.n, c->wn_sum, c->wn_cnt, st);
+    return 1;
+  };
+  if (int rc = scan_chunks(c, s, &total)) return rc;
   c->stats = total;
   return RNAMC_OK;
 }
@@ -180,17 +141,16 @@ int bpp_windowed_finish(rnamc_ctx* c, const WindowPlan& wp, const int64_t* sum, 
   const uint64_t cells = static_cast<uint64_t>(wp.band) * wp.n;
   if (sum) {  // the totals of a pool's shards
     HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(grow_device(reinterpret_cast<void**>(&c->wn_sum), &c->wn_sum_cap, cells * sizeof(int64_t)));
-    HIPCHK(grow_device(reinterpret_cast<void**>(&c->wn_cnt), &c->wn_cnt_cap, cells * sizeof(uint32_t)));
+    HIPCHK(c->wn_sum.grow(cells));
+    HIPCHK(c->wn_cnt.grow(cells));
     HIPCHK(hipMemcpyAsync(c->wn_sum, sum, cells * sizeof(int64_t), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(c->wn_cnt, cnt, cells * sizeof(uint32_t), hipMemcpyHostToDevice, st));
   }
-  HIPCHK(grow_device(reinterpret_cast<void**>(&c->wn_band), &c->wn_band_cap, cells * sizeof(float)));
-  if (paired_prob)
-    HIPCHK(grow_device(reinterpret_cast<void**>(&c->wn_paired), &c->wn_paired_cap, wp.n * sizeof(float)));
+  HIPCHK(c->wn_band.grow(cells));
+  if (paired_prob) HIPCHK(c->wn_paired.grow(wp.n));
   const bool prof = c->profile != 0;
   if (prof) {
-    if (int rc = event_pairs(&c->wn_events, 1)) return rc;
+    HIPCHK(c->wn_events.pairs(1));
     HIPCHK(hipEventRecord(c->wn_events[0], st));
   }
   const WindowGeom g = geom_of(wp);
@@ -208,8 +168,7 @@ int bpp_windowed_finish(rnamc_ctx* c, const WindowPlan& wp, const int64_t* sum, 
   HIPCHK(hipStreamSynchronize(st));
   c->stats.launches_other += launches;
   c->stats.launches_window += launches;
-  if (prof)
-    if (int rc = event_pairs_ms(c->wn_events, 1, &c->stats.ms_window)) return rc;
+  if (prof) HIPCHK(c->wn_events.pairs_ms(1, &c->stats.ms_window));
   return RNAMC_OK;
 }
 

@@ -26,10 +26,8 @@ int ensure_hp_init(rnamc_ctx* c, uint32_t max_n) {
   uint32_t len = std::max<uint32_t>(max_n + 1, 64);
   std::vector<float> hp(len);
   hp_init_table(c->host_params.turner, len, hp.data());
-  if (c->d_hp_init) HIPCHK(hipFree(c->d_hp_init));
-  c->d_hp_init = nullptr;
   c->hp_init_len = 0;
-  HIPCHK(hipMalloc(&c->d_hp_init, sizeof(float) * len));
+  HIPCHK(c->d_hp_init.replace_exact(len));
   HIPCHK(hipMemcpy(c->d_hp_init, hp.data(), sizeof(float) * len, hipMemcpyHostToDevice));
   c->hp_init_len = len;
   c->h_hp_init = std::move(hp);
@@ -112,11 +110,7 @@ uint32_t BatchPlan::active(size_t g, uint32_t d) const {
 }
 
 int BatchPlan::create_events() {
-  while (c->profile != 0 && c->events.size() < n_groups() * 4) {
-    hipEvent_t e;
-    HIPCHK(hipEventCreate(&e));
-    c->events.push_back(e);
-  }
+  if (c->profile != 0) HIPCHK(c->events.grow(n_groups() * 4));
   return RNAMC_OK;
 }
 
@@ -125,31 +119,16 @@ int BatchPlan::finish(hipStream_t st) {
   c->stats.workspace_bytes = c->ws_floats * sizeof(float);
   if (c->profile == 0) return RNAMC_OK;
   HIPCHK(hipStreamSynchronize(st));
+  const hipEvent_t* const gev = c->events.data();
   for (size_t g = 0; g < n_groups(); g++) {
     float a = 0, bms = 0, cc = 0;
-    HIPCHK(hipEventElapsedTime(&a, c->events[4 * g + 0], c->events[4 * g + 1]));
-    HIPCHK(hipEventElapsedTime(&bms, c->events[4 * g + 1], c->events[4 * g + 2]));
-    HIPCHK(hipEventElapsedTime(&cc, c->events[4 * g + 2], c->events[4 * g + 3]));
+    HIPCHK(hipEventElapsedTime(&a, gev[4 * g + 0], gev[4 * g + 1]));
+    HIPCHK(hipEventElapsedTime(&bms, gev[4 * g + 1], gev[4 * g + 2]));
+    HIPCHK(hipEventElapsedTime(&cc, gev[4 * g + 2], gev[4 * g + 3]));
     c->stats.ms_inside += a;
     c->stats.ms_outside += bms;
     c->stats.ms_other += cc;
   }
-  return RNAMC_OK;
-}
-
-int upload_descs(void** d, uint64_t* cap, const void* h, uint64_t count, uint64_t elem_bytes, hipStream_t st) {
-  if (*cap < count) {
-    if (*d) {
-      HIPCHK(hipDeviceSynchronize());
-      HIPCHK(hipFree(*d));
-      *d = nullptr;
-      *cap = 0;
-    }
-    const uint64_t want = std::max<uint64_t>(count, 1024);
-    HIPCHK(hipMalloc(d, want * elem_bytes));
-    *cap = want;
-  }
-  HIPCHK(hipMemcpyAsync(*d, h, count * elem_bytes, hipMemcpyHostToDevice, st));
   return RNAMC_OK;
 }
 
@@ -187,13 +166,17 @@ int run_batch(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* d_bases, const uint6
       });
   rc = ensure_ws(c, plan.max_group_floats);
   if (rc) return rc;
-  rc = upload_descs(reinterpret_cast<void**>(&c->d_seqs), &c->seqs_cap, c->descs.data(), c->descs.size(),
-                    sizeof(SeqDesc), st);
+  rc = upload_descs(c->d_seqs, c->descs, st);
   if (rc) return rc;
   const size_t n_groups = plan.n_groups();
   const bool prof = c->profile != 0;
   rc = plan.create_events();
   if (rc) return rc;
+  // the launch loops below read the context's events and second stream as plain handles
+  const hipEvent_t* const gev = c->events.data();
+  const hipEvent_t* const ev_a = c->ev_a.data();
+  const hipEvent_t* const ev_b = c->ev_b.data();
+  hipStream_t const aux = c->aux_stream;
   const uint32_t block = static_cast<uint32_t>(c->block_threads);
   const uint32_t dmin_in = contra ? 0u : (RNAMC_MIN_SPAN_HAIRPIN_CLOSE - 1);
   const uint32_t dmin_out = (contra && allows_short) ? 1u : (RNAMC_MIN_SPAN_HAIRPIN_CLOSE - 1);
@@ -220,7 +203,7 @@ int run_batch(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* d_bases, const uint6
     b.order_inside = static_cast<int>(c->order_inside);
     b.order_outside = static_cast<int>(c->order_outside);
     auto active = [&](uint32_t d) { return plan.active(g, d); };
-    if (prof) HIPCHK(hipEventRecord(c->events[4 * g + 0], st));
+    if (prof) HIPCHK(hipEventRecord(gev[4 * g + 0], st));
     launch_init(b, nseq, gmax, st);
     c->stats.launches_other++;
     if (opts.maxplus) {
@@ -230,7 +213,7 @@ int run_batch(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* d_bases, const uint6
       for (uint32_t d = dmin_in; d < gmax; d++) launch_mfe_inside(b, contra, d, d + 1, gmax, active(d), st);
       c->stats.launches_inside += gmax - dmin_in + 1;
       if (prof)
-        for (int e = 1; e <= 3; e++) HIPCHK(hipEventRecord(c->events[4 * g + e], st));
+        for (int e = 1; e <= 3; e++) HIPCHK(hipEventRecord(gev[4 * g + e], st));
       HIPCHK(hipGetLastError());
       if (hooks) {
         rc = hooks->after(g, gb, nseq);
@@ -310,18 +293,18 @@ int run_batch(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* d_bases, const uint6
         const bool merged = wave_form && c->lat_pairs != 0 && c->lat_merge != 0;
         if (pair_next && do_pair && !merged) {
           if (!have_a) {  // everything so far is on `st`
-            HIPCHK(hipEventRecord(c->ev_a[pv], st));
+            HIPCHK(hipEventRecord(ev_a[pv], st));
             have_a = true;
           }
-          HIPCHK(hipStreamWaitEvent(c->aux_stream, c->ev_a[pv], 0));
+          HIPCHK(hipStreamWaitEvent(aux, ev_a[pv], 0));
           if (c->lat_pairs != 0) {
-            launch_pair_lat(b, contra, false, d + 1, gmax, active(d + 1), c->aux_stream);
+            launch_pair_lat(b, contra, false, d + 1, gmax, active(d + 1), aux);
           } else {
-            launch_inside(b, contra, d, gmax, active(d + 1), block, false, true, c->aux_stream);
+            launch_inside(b, contra, d, gmax, active(d + 1), block, false, true, aux);
           }
           c->stats.launches_inside++;
         }
-        if (have_b) HIPCHK(hipStreamWaitEvent(st, c->ev_b[pv], 0));
+        if (have_b) HIPCHK(hipStreamWaitEvent(st, ev_b[pv], 0));
         if (do_sums) {
           const uint32_t pair_d = (merged && pair_next && do_pair) ? d + 1 : 0;
           if (wave_form || combine_due) {
@@ -338,18 +321,18 @@ int run_batch(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* d_bases, const uint6
         if (merged) {
           have_a = false;  // (recorded when a later diagonal needs it)
         } else {
-          HIPCHK(hipEventRecord(c->ev_a[cu], st));
+          HIPCHK(hipEventRecord(ev_a[cu], st));
           have_a = true;
         }
         if (pair_next) {
-          if (!merged) HIPCHK(hipEventRecord(c->ev_b[cu], c->aux_stream));
+          if (!merged) HIPCHK(hipEventRecord(ev_b[cu], aux));
           have_b = !merged;
           pairs_done = heads_done = d + 1;
         } else {
           have_b = false;
         }
       }
-      if (have_b) HIPCHK(hipStreamWaitEvent(st, c->ev_b[(gmax - 1) % ring], 0));
+      if (have_b) HIPCHK(hipStreamWaitEvent(st, ev_b[(gmax - 1) % ring], 0));
       if (combine_due)  // combine of the last diagonal
         launch_inside_lat(b, contra, gmax, gmax, active(gmax - 1), 0, true, 0, st);
     }
@@ -377,7 +360,7 @@ int run_batch(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* d_bases, const uint6
         d += 1;
       }
     }
-    if (prof) HIPCHK(hipEventRecord(c->events[4 * g + 1], st));
+    if (prof) HIPCHK(hipEventRecord(gev[4 * g + 1], st));
     // (rnamc_fold_scores needs the sums_close key set only: no outside sweep; the output
     // triangle then holds -1 / expf of stale log-probabilities and is not looked at)
     if (!opts.inside_only)
@@ -398,13 +381,9 @@ int run_batch(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* d_bases, const uint6
           return;
         }
         const size_t x = c->kev_class.size();
-        while (c->kev.size() < 2 * (x + 1)) {
-          hipEvent_t e = nullptr;
-          if (hipEventCreate(&e) != hipSuccess) {  // out of events: stop timing, keep running
-            launch();
-            return;
-          }
-          c->kev.push_back(e);
+        if (c->kev.grow(2 * (x + 1)) != hipSuccess) {  // out of events: stop timing, keep running
+          launch();
+          return;
         }
         (void)hipEventRecord(c->kev[2 * x], s);
         launch();
@@ -432,11 +411,11 @@ int run_batch(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* d_bases, const uint6
           const uint32_t na = active(d >= 1 ? d - 1 : 0);
           const uint32_t pv = (d + 1) % ring, cu = d % ring;
           if (first) {
-            HIPCHK(hipEventRecord(c->ev_a[pv], st));
+            HIPCHK(hipEventRecord(ev_a[pv], st));
           } else {
-            HIPCHK(hipStreamWaitEvent(st, c->ev_b[pv], 0));
+            HIPCHK(hipStreamWaitEvent(st, ev_b[pv], 0));
           }
-          HIPCHK(hipStreamWaitEvent(c->aux_stream, c->ev_a[pv], 0));
+          HIPCHK(hipStreamWaitEvent(aux, ev_a[pv], 0));
           if (d < gmax) {
             if (c->lat_split != 0) {
               timed(1, st, [&]() { launch_outside_lat(b, contra, d, gmax, active(d), r_mb, false, false, st); });
@@ -446,21 +425,21 @@ int run_batch(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* d_bases, const uint6
             }
             c->stats.launches_outside++;
           }
-          HIPCHK(hipEventRecord(c->ev_a[cu], st));
+          HIPCHK(hipEventRecord(ev_a[cu], st));
           if (head && r_head) {
-            timed(3, c->aux_stream, [&]() {
+            timed(3, aux, [&]() {
               if (c->lat_pairs != 0) {
-                launch_pair_lat(b, contra, true, d - 1, gmax, na, c->aux_stream);
+                launch_pair_lat(b, contra, true, d - 1, gmax, na, aux);
               } else {
-                launch_outside(b, contra, d, gmax, na, block, false, false, true, 4, c->aux_stream);
+                launch_outside(b, contra, d, gmax, na, block, false, false, true, 4, aux);
               }
             });
             c->stats.launches_outside++;
           }
-          HIPCHK(hipEventRecord(c->ev_b[cu], c->aux_stream));
+          HIPCHK(hipEventRecord(ev_b[cu], aux));
           first = false;
         }
-        if (!first) HIPCHK(hipStreamWaitEvent(st, c->ev_b[dmin_out % ring], 0));
+        if (!first) HIPCHK(hipStreamWaitEvent(st, ev_b[dmin_out % ring], 0));
       }
       for (uint32_t d = gmax + 1; d-- > dmin_out && !lat;) {
         const bool head = d >= 1 && d - 1 >= dmin_out;
@@ -472,7 +451,7 @@ int run_batch(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* d_bases, const uint6
                                static_cast<uint64_t>(gmax - d) * na >= c->dual_min_cells;
         if (!want_dual) {
           if (dual) {  // back to one stream: wait for the other kernel of d+1
-            HIPCHK(hipStreamWaitEvent(st, c->ev_b[(d + 1) % ring], 0));
+            HIPCHK(hipStreamWaitEvent(st, ev_b[(d + 1) % ring], 0));
             dual = false;
           }
           timed(2, st, [&]() {
@@ -481,33 +460,33 @@ int run_batch(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* d_bases, const uint6
           c->stats.launches_outside++;
         } else {
           // both kernels of diagonal d need both kernels of diagonal d+1
-          hipEvent_t ea = c->ev_a[d % ring], eb = c->ev_b[d % ring];
+          hipEvent_t ea = ev_a[d % ring], eb = ev_b[d % ring];
           const uint32_t pv = (d + 1) % ring;
           if (!dual) {
             // first two-kernel diagonal: everything so far is on `st`
-            HIPCHK(hipEventRecord(c->ev_a[pv], st));
+            HIPCHK(hipEventRecord(ev_a[pv], st));
           } else {
-            HIPCHK(hipStreamWaitEvent(st, c->ev_b[pv], 0));
+            HIPCHK(hipStreamWaitEvent(st, ev_b[pv], 0));
           }
-          HIPCHK(hipStreamWaitEvent(c->aux_stream, c->ev_a[pv], 0));
+          HIPCHK(hipStreamWaitEvent(aux, ev_a[pv], 0));
           timed(0, st, [&]() {
             launch_outside(b, contra, d, gmax, na, block, r_mb, false, head && r_head, 5, st);
           });
           HIPCHK(hipEventRecord(ea, st));
-          timed(1, c->aux_stream, [&]() {
-            launch_outside(b, contra, d, gmax, na, block, false, r_tail, false, 2, c->aux_stream);
+          timed(1, aux, [&]() {
+            launch_outside(b, contra, d, gmax, na, block, false, r_tail, false, 2, aux);
           });
-          HIPCHK(hipEventRecord(eb, c->aux_stream));
+          HIPCHK(hipEventRecord(eb, aux));
           c->stats.launches_outside += 2;
           dual = true;
         }
       }
-      if (dual) HIPCHK(hipStreamWaitEvent(st, c->ev_b[dmin_out % ring], 0));
+      if (dual) HIPCHK(hipStreamWaitEvent(st, ev_b[dmin_out % ring], 0));
     }
-    if (prof) HIPCHK(hipEventRecord(c->events[4 * g + 2], st));
+    if (prof) HIPCHK(hipEventRecord(gev[4 * g + 2], st));
     launch_finalize(b, nseq, gmax, dmin_out, st);
     c->stats.launches_other++;
-    if (prof) HIPCHK(hipEventRecord(c->events[4 * g + 3], st));
+    if (prof) HIPCHK(hipEventRecord(gev[4 * g + 3], st));
     HIPCHK(hipGetLastError());
     if (hooks) {
       rc = hooks->after(g, gb, nseq);

@@ -112,7 +112,7 @@ void build_tree_tabs(const rnamc_params& P, TreeTabs& T) {
 
 int ensure_tree_tabs(rnamc_ctx* c, hipStream_t st) {
   if (c->tree_tabs_valid && c->d_tree_tabs) return RNAMC_OK;
-  if (!c->d_tree_tabs) HIPCHK(hipMalloc(&c->d_tree_tabs, sizeof(TreeTabs)));
+  if (!c->d_tree_tabs) HIPCHK(c->d_tree_tabs.replace_exact(1));
   static thread_local TreeTabs tabs;  // (16 KB: not on the stack; the copy below is synchronous)
   build_tree_tabs(c->host_params, tabs);
   HIPCHK(hipStreamSynchronize(st));
@@ -150,7 +150,7 @@ int run_batch_tree(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* d_bases, const 
   if (band && !c->bulk_stream) {
     int lo = 0, hi = 0;
     (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-    HIPCHK(hipStreamCreateWithPriority(&c->bulk_stream, hipStreamNonBlocking, lo));
+    HIPCHK(hipStreamCreateWithPriority(c->bulk_stream.put(), hipStreamNonBlocking, lo));
   }
   if (band) {
     // The banded sweep lives on the mid-field kernels running BESIDE it.  Whether the side stream
@@ -245,22 +245,18 @@ int run_batch_tree(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* d_bases, const 
     // takes the two streams the context created first for the reference-order path, idle in this mode)
     c->dual_stream = c->aux_stream;
     c->bulk_stream2 = c->own_stream;
-    HIPCHK(hipEventCreateWithFlags(&c->ev_dual, hipEventDisableTiming));
-    for (size_t x = 0; x < c->ev_a.size(); x++) {
-      hipEvent_t ea, eb;
-      HIPCHK(hipEventCreateWithFlags(&ea, hipEventDisableTiming));
-      HIPCHK(hipEventCreateWithFlags(&eb, hipEventDisableTiming));
-      c->ev_a2.push_back(ea);
-      c->ev_b2.push_back(eb);
-    }
+    HIPCHK(hipEventCreateWithFlags(c->ev_dual.put(), hipEventDisableTiming));
+    HIPCHK(c->ev_a2.grow(c->ev_a.size()));
+    HIPCHK(c->ev_b2.grow(c->ev_a.size()));
   }
-  rc = upload_descs(reinterpret_cast<void**>(&c->d_tseqs), &c->tseqs_cap, tseqs.data(), tseqs.size(),
-                    sizeof(TreeSeq), st);
+  rc = upload_descs(c->d_tseqs, tseqs, st);
   if (rc) return rc;
   const size_t n_groups = plan.n_groups();
   const bool prof = c->profile != 0;
   rc = plan.create_events();
   if (rc) return rc;
+  const hipEvent_t* const gev = c->events.data();  // (the launch loops below read plain handles)
+  hipStream_t const bulk = c->bulk_stream;
   const uint32_t dmin_in = contra ? 0u : (RNAMC_MIN_SPAN_HAIRPIN_CLOSE - 1);
   const uint32_t dmin_out = (contra && allows_short) ? 1u : (RNAMC_MIN_SPAN_HAIRPIN_CLOSE - 1);
   if (dual) {  // (the second stream starts behind whatever the caller's stream holds: the descriptors' copy)
@@ -270,9 +266,9 @@ int run_batch_tree(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* d_bases, const 
   for (size_t g = 0; g < n_groups; g++) {
     const bool odd = dual && (g & 1u) != 0u;
     hipStream_t gst = odd ? c->dual_stream : st;
-    hipStream_t gbulk = odd ? c->bulk_stream2 : c->bulk_stream;
-    std::vector<hipEvent_t>& gev_a = odd ? c->ev_a2 : c->ev_a;
-    std::vector<hipEvent_t>& gev_b = odd ? c->ev_b2 : c->ev_b;
+    hipStream_t gbulk = odd ? c->bulk_stream2 : bulk;
+    const hipEvent_t* const gev_a = (odd ? c->ev_a2 : c->ev_a).data();
+    const hipEvent_t* const gev_b = (odd ? c->ev_b2 : c->ev_b).data();
     const uint32_t gb = c->group_begin[g], ge = c->group_begin[g + 1];
     const uint32_t nseq = ge - gb;
     const uint32_t gmax = c->descs[gb].n;
@@ -300,7 +296,7 @@ int run_batch_tree(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* d_bases, const 
     b.cons = opts.cons;
     b.max_span = opts.max_span;
     auto active = [&](uint32_t d) { return plan.active(g, d); };
-    if (prof) HIPCHK(hipEventRecord(c->events[4 * g + 0], gst));
+    if (prof) HIPCHK(hipEventRecord(gev[4 * g + 0], gst));
     launch_tree_init(b, nseq, gmax, contra, 0, gst);
     launch_tree_static(b, contra, nseq, gmax, gst);
     c->stats.launches_other += 2;
@@ -424,7 +420,7 @@ int run_batch_tree(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* d_bases, const 
         HIPCHK(hipEventRecord(gev_b[(cur_band + 1) % ering], gbulk));
         HIPCHK(hipStreamWaitEvent(gst, gev_b[(cur_band + 1) % ering], 0));
       }
-      if (prof) HIPCHK(hipEventRecord(c->events[4 * g + 1], gst));
+      if (prof) HIPCHK(hipEventRecord(gev[4 * g + 1], gst));
 #ifdef RNAMC_DEBUG_KNOBS
       if (const char* dump = getenv("RNAMC_DUMP_MID")) {  // "<first slot>,<slots>,<path>": after the inside sweep
         int s0 = 0, ns = 1;
@@ -525,7 +521,7 @@ int run_batch_tree(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* d_bases, const 
       launch_tree_inside(b, contra, d, gmax, active(d), c->tree_tpc, two, 0u, false, 0u, 0u, c->tree_pol, gst);
       c->stats.launches_inside++;
     }
-    if (prof) HIPCHK(hipEventRecord(c->events[4 * g + 1], gst));
+    if (prof) HIPCHK(hipEventRecord(gev[4 * g + 1], gst));
     launch_tree_init(b, nseq, gmax, contra, 1, gst);
     c->stats.launches_other++;
     if (two) {
@@ -547,10 +543,10 @@ int run_batch_tree(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* d_bases, const 
       c->stats.launches_outside++;
     }
     }
-    if (prof) HIPCHK(hipEventRecord(c->events[4 * g + 2], gst));
+    if (prof) HIPCHK(hipEventRecord(gev[4 * g + 2], gst));
     launch_tree_finalize(b, nseq, gmax, gst);
     c->stats.launches_other++;
-    if (prof) HIPCHK(hipEventRecord(c->events[4 * g + 3], gst));
+    if (prof) HIPCHK(hipEventRecord(gev[4 * g + 3], gst));
     HIPCHK(hipGetLastError());
     if (hooks) {
       rc = hooks->after(g, gb, nseq);

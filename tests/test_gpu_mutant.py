@@ -320,6 +320,37 @@ def test_profiled_call_times_the_mutant_kernels(ctx):
     assert ctx.stats()["ms_mutant"] == 0
 
 
+def test_chunks_groups_and_profile_together(ctx):
+    """several chunks, several groups a chunk and a profiled call at once: 60 bases are 180 mutants; 600
+    nucleotides a chunk are 18 chunks of 10 mutants, three mutants a group are four groups a chunk.  The same
+    bytes as the call of one chunk and one group, and the statistics of the whole call: the wild type's group and
+    its paired launch, then a compare and a paired launch per group"""
+    reset(ctx)
+    seq = seq_of(60)
+    base = ctx.mutant_scan(seq, False, False)
+    plain = ctx.stats()
+    assert len(base) == 180 and plain["n_groups"] == 2 and plain["launches_mutant"] == 3 and plain["ms_mutant"] == 0
+    try:
+        ctx.set("mutant_chunk_nt", 600)
+        ctx.set("group_max_seqs", 3)
+        counts = []
+        for profile in (0, 1):
+            ctx.set("profile", profile)
+            same_scan(ctx.mutant_scan(seq, False, False), base)
+            st = ctx.stats()
+            assert st["n_groups"] == 1 + 18 * 4 and st["launches_mutant"] == 1 + 2 * 72
+            assert st["launches_other"] >= st["launches_mutant"] + st["n_groups"]
+            assert st["launches_inside"] >= 73 and st["launches_outside"] >= 73
+            assert st["workspace_bytes"] == plain["workspace_bytes"]  # (the context's workspace never shrinks)
+            assert (0 < st["ms_mutant"] < 1e3 and st["ms_inside"] > 0 and st["ms_outside"] > 0) if profile else \
+                (st["ms_mutant"] == 0 and st["ms_inside"] == 0 and st["ms_outside"] == 0)
+            counts.append({k: v for k, v in st.items() if not k.startswith("ms_")})
+        assert counts[0] == counts[1]  # (timing a call changes none of its counts)
+    finally:
+        ctx.set("profile", 0)
+        reset(ctx)
+
+
 def test_tree_order_mode(ctx):
     """summation mode 1: against the dense entry in mode 1 with the same call structure, the wild type alone,
     then the chunk's records"""

@@ -239,6 +239,42 @@ def test_invariance(ctx, params):
         pool.close()
 
 
+def test_chunks_groups_and_profile_together(ctx):
+    """several chunks, several groups a chunk and a profiled call at once: (2000, 200, 100) is 19 windows; 1000
+    nucleotides a chunk are 5 + 5 + 5 + 4 windows, three windows a group are two groups a chunk.  The same bytes
+    as the call of one chunk and one group, and the statistics of the whole call: a window launch per group, then
+    the finalize and the paired launch"""
+    reset(ctx)
+    n, w, s = 2000, 200, 100
+    seq = seq_of(n)
+    base = ctx.bpp_windowed(seq, w, False, False, stride=s)
+    plain = ctx.stats()
+    assert len(base.starts) == 19 and plain["n_groups"] == 1 and plain["launches_window"] == 3
+    assert plain["ms_window"] == 0
+    try:
+        ctx.set("window_chunk_nt", 1000)
+        ctx.set("group_max_seqs", 3)
+        counts = []
+        for profile in (0, 1):
+            ctx.set("profile", profile)
+            res = ctx.bpp_windowed(seq, w, False, False, stride=s)
+            st = ctx.stats()
+            assert np.array_equal(res.band.view(np.uint32), base.band.view(np.uint32))
+            assert np.array_equal(res.paired_prob.view(np.uint32), base.paired_prob.view(np.uint32))
+            assert np.array_equal(res.window_log_z.view(np.uint32), base.window_log_z.view(np.uint32))
+            assert st["n_groups"] == 8 and st["launches_window"] == 8 + 2
+            assert st["launches_other"] >= st["launches_window"] + st["n_groups"]
+            assert st["launches_inside"] >= 8 and st["launches_outside"] >= 8
+            assert st["workspace_bytes"] == plain["workspace_bytes"]  # (the context's workspace never shrinks)
+            assert (0 < st["ms_window"] < 1e3 and st["ms_inside"] > 0 and st["ms_outside"] > 0) if profile else \
+                (st["ms_window"] == 0 and st["ms_inside"] == 0 and st["ms_outside"] == 0)
+            counts.append({k: v for k, v in st.items() if not k.startswith("ms_")})
+        assert counts[0] == counts[1]  # (timing a call changes none of its counts)
+    finally:
+        ctx.set("profile", 0)
+        reset(ctx)
+
+
 def test_tree_order_mode(ctx):
     """summation mode 1: against the dense entry in mode 1 on the identical window batch"""
     reset(ctx)
