@@ -458,18 +458,24 @@ class Context:
 
     @classmethod
     def of_pool(cls, pool, idx=0):
-        """Context `idx` of a Pool as a Context (owned by the pool: close() leaves it alone)."""
+        """Context `idx` of a Pool as a Context (owned by the pool: close() leaves it alone).
+        A borrowed context syncs through its pool: it keeps no key of its own, and its sync_params is
+        the pool's, so every context of the pool and the pool's key change together."""
         self = cls.__new__(cls)
         self._h = C.c_void_p(_lib.lib().rnamc_pool_ctx(pool._h, idx))
         if not self._h:
             raise IndexError(idx)
         self._owned = False
-        self._key = pool._key
-        self._pool = pool  # keeps the owner alive
+        self._pool = pool  # keeps the owner alive; holds the key of the tables on the device
         return self
 
     def sync_params(self, fold_score_sets):
-        """Upload the tables again if their contents differ from the ones on the device."""
+        """Upload the tables again if their contents differ from the ones on the device (a context
+        borrowed from a Pool: on every context of that pool)."""
+        pool = getattr(self, "_pool", None)
+        if pool is not None:
+            pool.sync_params(fold_score_sets)
+            return
         key = fold_score_sets.content_key()
         if key != self._key:
             _lib.check(_lib.lib().rnamc_ctx_set_params(self._h, fold_score_sets.ptr))
@@ -662,7 +668,9 @@ class Context:
 class Pool:
     """Owns one rnamc_pool: a device context per listed GPU (devices=None: every visible one);
     `bpp_batch` shards a batch over them inside librnamc (rnamc_bpp_batch_multi), one host
-    thread per device, results written straight into the host triangles."""
+    thread per device, results written straight into the host triangles.  The pool holds the key of
+    the tables its contexts were last given; a context borrowed with Context.of_pool syncs through
+    its pool, never on its own."""
 
     def __init__(self, fold_score_sets, devices=None, workspace_bytes=0):
         self._h = C.c_void_p()
@@ -679,6 +687,7 @@ class Pool:
         return int(_lib.lib().rnamc_pool_size(self._h))
 
     def sync_params(self, fold_score_sets):
+        """Upload the tables to every context of the pool if their contents differ from the ones there."""
         key = fold_score_sets.content_key()
         if key != self._key:
             _lib.check(_lib.lib().rnamc_pool_set_params(self._h, fold_score_sets.ptr))
@@ -797,7 +806,6 @@ def _context_for(fold_score_sets):
         pool = _pool_for(fold_score_sets)  # (uploads changed tables to every context, this one included)
         if _ctx is None:
             _ctx = Context.of_pool(pool, 0)
-        _ctx._key = pool._key
         return _ctx
 
 
@@ -829,13 +837,15 @@ def get_fold_sums(seq, fold_score_sets):
     """`get_fold_sums<T>(seq, &mut fold_scores) -> FoldSums<T>` (src/mccaskill_algo.rs:282-378,
     Turner) on the device.  The reference also fills `fold_scores` on the way; here that is
     `mccaskill_algo(...)[1]` / `Context.fold_scores_packed`."""
-    return _context_for(fold_score_sets).fold_sums(seq, False, False)
+    with _ctx_lock:  # (as every function here: the tables stay the caller's until the call returns)
+        return _context_for(fold_score_sets).fold_sums(seq, False, False)
 
 
 def get_fold_sums_contra(seq, allows_short_hairpins, fold_score_sets):
     """`get_fold_sums_contra<T>(seq, &mut fold_scores, allows_short_hairpins, fold_score_sets)`
     (src/mccaskill_algo.rs:380-516) on the device."""
-    return _context_for(fold_score_sets).fold_sums(seq, True, allows_short_hairpins)
+    with _ctx_lock:
+        return _context_for(fold_score_sets).fold_sums(seq, True, allows_short_hairpins)
 
 
 def mccaskill_algo_batch(seqs, uses_contra_model, allows_short_hairpins, fold_score_sets,
