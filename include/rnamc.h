@@ -384,6 +384,14 @@ int rnamc_ctx_stats(rnamc_ctx* ctx, void* out, uint64_t out_bytes, uint64_t* lib
  * sums_accessible, 2 sums_external, 3 sums_1ormore_basepairs, 4
  * multibranch_close_scores, 5 probs_multibranch, 6 probs_multibranch2. */
 int rnamc_debug_fetch(rnamc_ctx* ctx, uint32_t seq_idx, int which, float* out_nxn);
+/* The same for the tree-order mode: the raw workspace matrix `slot` (0 .. 37, enum TreeMat of
+ * rna_algos_amd/csrc/rnamc_device.h; an internal layout, for tests only) of sequence `seq_idx` as the
+ * last call left it, *ld (may be NULL) = its row stride.  With out = NULL only *ld and *floats (may be
+ * NULL; the matrix's size) are set.  "row": cell (i, j) at [i * ld + j], "col": [j * ld + i],
+ * diagonal-major: [(j - i) * ld + i].  RNAMC_ERR_INVALID_ARG unless the last batch call of the context
+ * ran in summation mode 1 and made ONE group, or when out_floats is below the matrix's size. */
+int rnamc_debug_fetch_tree(rnamc_ctx* ctx, uint32_t seq_idx, int slot, float* out, uint64_t out_floats,
+                           uint32_t* ld, uint64_t* floats);
 
 /* ------------------------------------------------------------------------- */
 /* FoldScores<T>, the second element of mccaskill_algo's result

@@ -274,4 +274,28 @@ int rnamc_debug_fetch(rnamc_ctx* c, uint32_t seq_idx, int which, float* out_nxn)
   return RNAMC_OK;
 }
 
+int rnamc_debug_fetch_tree(rnamc_ctx* c, uint32_t seq_idx, int slot, float* out, uint64_t out_floats, uint32_t* ld,
+                           uint64_t* floats) {
+  if (!c || slot < 0 || slot >= rnamc::T_COUNT) return RNAMC_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> lock(c->mu);
+  // (h_tseqs is emptied when a call starts and filled by the tree-order sweep alone; one group: the
+  // descriptors' offsets are relative to the workspace itself)
+  if (c->group_begin.size() != 2 || c->h_tseqs.empty() || c->h_tseqs.size() != c->descs.size())
+    return RNAMC_ERR_INVALID_ARG;
+  const rnamc::TreeSeq* ts = nullptr;
+  for (const rnamc::TreeSeq& t : c->h_tseqs)
+    if (t.batch_idx == seq_idx) ts = &t;
+  if (!ts) return RNAMC_ERR_INVALID_ARG;
+  if (ld) *ld = ts->ld;
+  if (floats) *floats = ts->msz;
+  if (!out) return RNAMC_OK;
+  if (out_floats < ts->msz) return RNAMC_ERR_INVALID_ARG;
+  DeviceGuard guard(c->device);
+  if (!guard.ok) return RNAMC_ERR_NO_DEVICE;
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy(out, c->d_ws + ts->ws_off + static_cast<uint64_t>(slot) * ts->msz, ts->msz * sizeof(float),
+                   hipMemcpyDeviceToHost));
+  return RNAMC_OK;
+}
+
 }  // extern "C"

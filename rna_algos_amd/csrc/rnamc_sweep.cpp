@@ -45,6 +45,7 @@ int BatchPlan::begin(rnamc_ctx* ctx, uint32_t n_seqs, const uint64_t* offsets) {
   c->descs.clear();
   c->group_begin.clear();
   c->group_out_floats.clear();
+  c->h_tseqs.clear();  // (the tree-order sweep fills it: rnamc_debug_fetch_tree tells by it which mode ran last)
   if (n_seqs == 0) return RNAMC_OK;
   for (uint32_t s = 0; s < n_seqs; s++) {
     if (offsets[s + 1] < offsets[s]) return RNAMC_ERR_INVALID_ARG;

@@ -664,6 +664,16 @@ class Context:
         _lib.check(_lib.lib().rnamc_debug_fetch(self._h, seq_idx, which, out.ctypes.data))
         return out
 
+    def debug_fetch_tree(self, seq_idx, slot):
+        """rnamc_debug_fetch_tree -> (raw workspace matrix `slot` of the last tree-order call as f32[rows, ld]
+        — whole rows only, the padding behind them dropped —, ld)"""
+        ld, floats = C.c_uint32(), C.c_uint64()
+        _lib.check(_lib.lib().rnamc_debug_fetch_tree(self._h, seq_idx, slot, None, 0, C.byref(ld), C.byref(floats)))
+        out = np.empty(floats.value, dtype=np.float32)
+        _lib.check(_lib.lib().rnamc_debug_fetch_tree(self._h, seq_idx, slot, out.ctypes.data, out.size, None, None))
+        rows = out.size // ld.value
+        return out[:rows * ld.value].reshape(rows, ld.value), ld.value
+
 
 class Pool:
     """Owns one rnamc_pool: a device context per listed GPU (devices=None: every visible one);

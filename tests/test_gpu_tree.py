@@ -152,7 +152,9 @@ def test_tree_vs_committed_exact_f64(ctx, params, name):
     order: ln Z = 1431 (n = 2048) / 2957 (n = 4096) carry ulps of 1.2e-4 / 2.4e-4, and a probability
     is the exp of a difference of such values — measured 7.2e-4 / 8.3e-4 at n = 2048; the bound is
     16 ulps of ln Z for both, and the reference-order result of the same library must sit FURTHER
-    from the exact value (it does, by an order of magnitude: its fold is approximate on top)."""
+    from the exact value (it does, by an order of magnitude: its fold is approximate on top).
+    Each fixture is folded as a LONE sequence: the wave-per-cell chain of rnamc_tree.hip, not the batch
+    form, which test_gpu_tree_batch_scale.py holds to the same fixtures."""
     import os
     if not os.path.exists(os.path.join(os.path.dirname(__file__), "golden", name + ".npz")):
         pytest.skip(f"{name}.npz not generated (python tests/make_golden.py exact|exact4096)")
@@ -362,7 +364,8 @@ def test_tree_lane_per_cell_batch(ctx, params, contra, short):
     """The batch form of the mode (rnamc_tree_lane.h: a lane per cell, diagonal-major operands, one
     diagonal per launch, bands spread into the row- / column-major copies of the mid-field kernels):
     a ragged batch, lengths 1 .. 900 around the band boundaries, against the f64 evaluation of the
-    recurrences (the mode's own bound) and against the wave-per-cell launches of the same mode (the
+    recurrences at those lengths (the mode's own bound; 1024 .. 4096 nt: test_gpu_tree_batch_scale.py)
+    and against the wave-per-cell launches of the same mode (the
     same terms grouped differently: rounding); band 32, the mid-field kernels a band ahead on the side
     stream instead of in front of the band, and the VALU form of the mid-field products instead of the
     matrix-core form (rnamc_tree_mx.h) too."""
@@ -404,7 +407,8 @@ def test_tree_batch_form_many_sequences(ctx, params, contra):
     a tile per wave in the matrix-core mid-field (k_tree_mid_mx<1>: at least 4 096 tiles a launch), the
     generic 2-loop sums three diagonals a launch (k_tlane_gen) against one diagonal a launch, 256 listed
     cells to a workgroup in the just-in-time role — against the wave-per-cell launches of the same mode
-    (rounding) and, for the two shortest, against the f64 evaluation of the recurrences."""
+    (rounding) and, for the two shortest (300 nt or little more), against the f64 evaluation of the
+    recurrences; the batch form against f64 at the benchmark's lengths: test_gpu_tree_batch_scale.py."""
     rng = np.random.default_rng(2026)
     lens = sorted((int(x) for x in rng.integers(300, 701, size=160)), reverse=True)
     seqs = [O.splitmix_seq(n, 31 * n + k) for k, n in enumerate(lens)]

@@ -319,12 +319,22 @@ def test_fold_sums_stage_is_the_inside_pass_of_the_whole_path():
                 assert np.all(fs["sums_external"][iu][short_span] == 0.0)
 
 
-def test_exact_fixture_reproduces(params):
-    """tests/golden/exact_n1024_seed1024_contra.npz (the f64 pin of the tree-order mode at scale,
-    tests/make_golden.py `exact`) is what oracle/mccaskill_exact.c gives today: drift guard of the
-    fixture and of its container (every 97th present pair, key-set sha256).  ~30 s."""
-    f = np.load(os.path.join(GOLD, "exact_n1024_seed1024_contra.npz"))
+EXACT_ALL = ["exact_n1024_seed1024_contra", "exact_n1024_seed1024_turner", "exact_n1531_seed1531_contra",
+             "exact_n1531_seed1531_turner", "exact_n2048_seed2048_contra_short", "exact_n2048_seed2048_turner",
+             "exact_n4096_seed4096_turner"]
+
+
+@pytest.mark.parametrize("name", ["exact_n1024_seed1024_contra", "exact_n1531_seed1531_contra"])
+def test_exact_fixture_reproduces(params, name):
+    """tests/golden/exact_n1024_seed1024_contra.npz and exact_n1531_seed1531_contra.npz (the f64 pins of the
+    tree-order mode at scale, tests/make_golden.py `exact`, `exact_mid`) are what oracle/mccaskill_exact.c
+    gives today: drift guard of the fixtures and of their container (every 97th present pair, key-set
+    sha256).  ~30 s and ~2.5 minutes.  The reference-order oracle's deviation at n = 1531, measured here:
+    max |dp| 7.8e-3, |d ln Z| 2.3e-2 — inside the band asserted at n = 1024."""
+    f = np.load(os.path.join(GOLD, name + ".npz"))
     n, seed = int(f["n"][0]), int(f["seed"][0])
+    short = int(f["short"][0]) if "short" in f.files else 0
+    assert int(f["contra"][0]) == 1 and short == 0
     xb, xz = O.exact_bpp(params.ptr, O.splitmix_seq(n, seed), 1, 0)
     pres = np.flatnonzero(xb >= -0.5)
     assert hashlib.sha256(pres.astype(np.uint32).tobytes()).digest() == bytes(f["keyset_sha256"])
@@ -333,4 +343,32 @@ def test_exact_fixture_reproduces(params):
     # and the f32 reference-order oracle sits where DESIGN.md section 4b says it does against it
     out, lz = O.bpp(params.ptr, O.splitmix_seq(n, seed), 1, 0)
     dp = float(np.max(np.abs(out[f["index"]].astype(np.float64) - f["prob"])))
+    print(f"{name}: reference-order oracle against f64: max |dp| = {dp:.3e}, |d ln Z| = {abs(float(lz) - xz):.3e}")
     assert 1e-4 < dp < 5e-2 and abs(float(lz) - xz) < 5e-2, (dp, float(lz), xz)
+
+
+@pytest.mark.parametrize("name", EXACT_ALL)
+def test_exact_fixtures_load(name):
+    """Every f64 fixture loads, and its container is consistent with itself — no oracle run: `index` is every
+    97th entry of a key set of the recorded `present` size (strictly increasing slots of the packed triangle,
+    ceil(present / 97) of them, the first one the key set's first), the probabilities are probabilities, `short`
+    is 0 where absent."""
+    f = np.load(os.path.join(GOLD, name + ".npz"))
+    n, present = int(f["n"][0]), int(f["present"][0])
+    assert f"_n{n}_seed{int(f['seed'][0])}_" in name
+    assert ("contra" in name) == bool(f["contra"][0])
+    assert (int(f["short"][0]) if "short" in f.files else 0) == (1 if name.endswith("_short") else 0)
+    idx = f["index"].astype(np.int64)
+    assert idx.size == len(range(0, present, 97)) and f["prob"].shape == idx.shape
+    assert np.all(np.diff(idx) >= 97) and idx[-1] < n * (n + 1) // 2
+    # (96 present slots lie between two picks, fewer than 97 behind the last)
+    assert (idx.size - 1) * 97 < present <= idx.size * 97
+    # the first present slot of the diagonal-major triangle: the first pair of the shortest admitted span
+    s = O.splitmix_seq(n, int(f["seed"][0]))
+    dmin = 1 if name.endswith("_short") else 4  # (f["index"][0] lies on the first diagonal that holds a pair)
+    t = s[:n - dmin].astype(np.int64) + s[dmin:]
+    first = dmin * n - dmin * (dmin - 1) // 2 + int(np.flatnonzero((t == 3) | (t == 5))[0])
+    assert idx[0] == first, (int(idx[0]), first)
+    assert f["keyset_sha256"].shape == (32,) and f["keyset_sha256"].dtype == np.uint8
+    assert np.all(f["prob"] >= 0.0) and np.all(f["prob"] <= 1.0 + 1e-12) and float(f["max_prob"][0]) <= 1.0 + 1e-12
+    assert np.isfinite(float(f["log_partition"][0])) and float(f["sum_present"][0]) >= float(f["prob"].sum())
