@@ -64,6 +64,8 @@ extern "C" {
   fn rnamc_bpp_batch_sparse_multi(pool: *mut RnamcPool, n_seqs: u32, bases: *const u8, offsets: *const u64, constraints: *const c_char, max_bp_span: u32, uses_contra_model: c_int, allows_short_hairpins: c_int, min_prob: f32, pair_start: *mut u64, pair_count: *mut u64, pair_i: *mut u32, pair_j: *mut u32, pair_prob: *mut f32, pairs_cap: u64, pairs_total: *mut u64, paired_prob: *mut f32, log_partition: *mut f32) -> c_int;
   fn rnamc_window_plan(n: u64, window: u32, stride: u32, max_bp_span: u32, n_windows: *mut u64, band: *mut u32, starts: *mut u64, starts_cap: u64) -> c_int;
   fn rnamc_bpp_windowed(ctx: *mut RnamcCtx, bases: *const u8, n: u64, constraint: *const c_char, window: u32, stride: u32, max_bp_span: u32, uses_contra_model: c_int, allows_short_hairpins: c_int, band_prob: *mut f32, paired_prob: *mut f32, window_log_partition: *mut f32) -> c_int;
+  fn rnamc_bpp_alignment(ctx: *mut RnamcCtx, n_rows: u32, n_cols: u32, rows: *const u8, max_bp_span: u32, uses_contra_model: c_int, allows_short_hairpins: c_int, centroid_thresholds: *const f32, n_thresholds: u32, bpp: *mut f32, col_paired: *mut f32, structs: *mut u8, n_pairs: *mut u32, expect_accuracy: *mut f32, log_partition: *mut f32, row_len: *mut u32) -> c_int;
+  fn rnamc_bpp_alignment_multi(pool: *mut RnamcPool, n_rows: u32, n_cols: u32, rows: *const u8, max_bp_span: u32, uses_contra_model: c_int, allows_short_hairpins: c_int, centroid_thresholds: *const f32, n_thresholds: u32, bpp: *mut f32, col_paired: *mut f32, structs: *mut u8, n_pairs: *mut u32, expect_accuracy: *mut f32, log_partition: *mut f32, row_len: *mut u32) -> c_int;
   fn rnamc_bpp_windowed_multi(pool: *mut RnamcPool, bases: *const u8, n: u64, constraint: *const c_char, window: u32, stride: u32, max_bp_span: u32, uses_contra_model: c_int, allows_short_hairpins: c_int, band_prob: *mut f32, paired_prob: *mut f32, window_log_partition: *mut f32) -> c_int;
   fn rnamc_mutant_plan(bases: *const u8, n: u32, positions: *const u32, n_positions: u32, n_mutants: *mut u64, mut_pos: *mut u32, mut_base: *mut u8, cap: u64) -> c_int;
   fn rnamc_mutant_scan(ctx: *mut RnamcCtx, bases: *const u8, n: u32, constraint: *const c_char, max_bp_span: u32, uses_contra_model: c_int, allows_short_hairpins: c_int, positions: *const u32, n_positions: u32, log_partition: *mut f32, pair_dist2_q: *mut i64, max_dp: *mut f32, max_i: *mut u32, max_j: *mut u32, paired_prob: *mut f32, wt_log_partition: *mut f32, wt_paired_prob: *mut f32) -> c_int;
@@ -461,6 +463,80 @@ pub fn mccaskill_algo_windowed(
     );
   });
   (band, paired_prob, band_width as usize)
+}
+
+// Alignment folding (rnamc_bpp_alignment_multi): the consumer of the crate's own read_align_clustal /
+// read_align_fasta / read_align_stockholm.  `cols` is their Cols (column-major, PSEUDO_BASE = a gap);
+// every row is folded without its gaps, the pair probabilities are averaged per COLUMN pair over all
+// rows on the device, and every threshold yields the gamma-centroid fold of the averaged matrix.
+// bpp is the packed diagonal-major triangle over the columns (-1 where no row had the pair).
+pub struct AlignmentBpp {
+  pub n_cols: usize,
+  pub bpp: Vec<f32>,
+  pub col_paired: Vec<f32>,
+  pub folds: Vec<(FoldStr, f32)>,
+  pub log_partition: Vec<f32>,
+  pub row_len: Vec<u32>,
+}
+
+pub fn alignment_fold(
+  cols: &Cols,
+  uses_contra_model: bool,
+  allows_short_hairpins: bool,
+  fold_score_sets: &FoldScoreSets,
+  centroid_thresholds: &[f32],
+  max_bp_span: u32,
+) -> AlignmentBpp {
+  let n_cols = cols.len();
+  let n_rows = if n_cols == 0 { 0 } else { cols[0].len() };
+  let mut rows = vec![PSEUDO_BASE as u8; n_rows * n_cols];
+  for (c, col) in cols.iter().enumerate() {
+    assert!(col.len() == n_rows, "ragged alignment column {}", c);
+    for (s, &x) in col.iter().enumerate() {
+      rows[s * n_cols + c] = x as u8;
+    }
+  }
+  let ng = centroid_thresholds.len();
+  let mut r = AlignmentBpp {
+    n_cols,
+    bpp: vec![-1f32; n_cols * (n_cols + 1) / 2],
+    col_paired: vec![0f32; n_cols],
+    folds: Vec::new(),
+    log_partition: vec![0f32; n_rows],
+    row_len: vec![0u32; n_rows],
+  };
+  let mut structs = vec![b'.'; ng * n_cols];
+  let mut n_pairs = vec![0u32; ng];
+  let mut expect_accuracy = vec![0f32; ng];
+  with_pool(fold_score_sets, |pool| {
+    check(
+      unsafe {
+        rnamc_bpp_alignment_multi(
+          pool,
+          n_rows as u32,
+          n_cols as u32,
+          rows.as_ptr(),
+          max_bp_span,
+          uses_contra_model as c_int,
+          allows_short_hairpins as c_int,
+          if ng == 0 { std::ptr::null() } else { centroid_thresholds.as_ptr() },
+          ng as u32,
+          r.bpp.as_mut_ptr(),
+          r.col_paired.as_mut_ptr(),
+          if ng == 0 { std::ptr::null_mut() } else { structs.as_mut_ptr() },
+          if ng == 0 { std::ptr::null_mut() } else { n_pairs.as_mut_ptr() },
+          if ng == 0 { std::ptr::null_mut() } else { expect_accuracy.as_mut_ptr() },
+          r.log_partition.as_mut_ptr(),
+          r.row_len.as_mut_ptr(),
+        )
+      },
+      "rnamc_bpp_alignment_multi",
+    );
+  });
+  for g in 0..ng {
+    r.folds.push((structs[g * n_cols..(g + 1) * n_cols].to_vec(), expect_accuracy[g]));
+  }
+  r
 }
 
 // Point-mutation scan of one sequence (rnamc_mutant_scan_multi; no counterpart in the reference

@@ -311,6 +311,41 @@ inline WindowedBpp mccaskill_algo_windowed(const Context& ctx, const Seq& seq, u
 }
 // the same over a pool's devices: rnamc_bpp_windowed_multi (same arguments, a rnamc_pool* first)
 
+// Alignment folding (rnamc_bpp_alignment; the consumer of the reference's read_align_* readers): the rows
+// of an alignment (n_rows x n_cols codes, row-major: 0..3 a base, 4 = PSEUDO_BASE a gap) folded without
+// their gaps, the pair probabilities averaged per COLUMN pair over all rows on the device, one
+// gamma-centroid fold of the averaged matrix per threshold.  bpp is the packed diagonal-major triangle
+// over the columns (rnamc_bpp_index(n_cols, ci, cj); -1 where no row had the pair).
+struct AlignmentBpp {
+  uint32_t n_cols = 0;
+  std::vector<float> bpp, col_paired, expect_accuracy, log_partition;
+  std::vector<std::string> folds;  // one dot-bracket string over the columns per threshold
+  std::vector<uint32_t> n_pairs, row_len;
+};
+inline AlignmentBpp alignment_fold(const Context& ctx, const std::vector<uint8_t>& rows, uint32_t n_rows,
+                                   uint32_t n_cols, bool uses_contra_model, bool allows_short_hairpins,
+                                   const std::vector<float>& centroid_thresholds = {}, uint32_t max_bp_span = 0) {
+  if (rows.size() != static_cast<size_t>(n_rows) * n_cols) check(RNAMC_ERR_INVALID_ARG);
+  AlignmentBpp r;
+  r.n_cols = n_cols;
+  const uint32_t ng = static_cast<uint32_t>(centroid_thresholds.size());
+  r.bpp.resize(rnamc_bpp_len(n_cols));
+  r.col_paired.resize(n_cols);
+  r.expect_accuracy.resize(ng);
+  r.n_pairs.resize(ng);
+  r.log_partition.resize(n_rows);
+  r.row_len.resize(n_rows);
+  std::vector<uint8_t> structs(static_cast<size_t>(ng) * n_cols);
+  check(rnamc_bpp_alignment(ctx.get(), n_rows, n_cols, rows.data(), max_bp_span, uses_contra_model,
+                            allows_short_hairpins, ng ? centroid_thresholds.data() : nullptr, ng, r.bpp.data(),
+                            r.col_paired.data(), ng ? structs.data() : nullptr, ng ? r.n_pairs.data() : nullptr,
+                            ng ? r.expect_accuracy.data() : nullptr, r.log_partition.data(), r.row_len.data()));
+  for (uint32_t g = 0; g < ng; g++)
+    r.folds.emplace_back(reinterpret_cast<const char*>(structs.data()) + static_cast<size_t>(g) * n_cols, n_cols);
+  return r;
+}
+// the same over a pool's devices: rnamc_bpp_alignment_multi (same arguments, a rnamc_pool* first)
+
 // Point-mutation scan of one sequence (rnamc_mutant_scan; no counterpart in the reference): every
 // single-base mutant of `positions` (empty: every base; three mutants per position, base codes ascending
 // without the wild type's) folded and its pair-probability matrix compared with the wild type's on the

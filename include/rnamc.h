@@ -42,7 +42,8 @@ extern "C" {
  *    rnamc_sample_batch_constrained, rnamc_mfe_batch_constrained, rnamc_log_partition_batch,
  *    rnamc_constraint_check, rnamc_centroid_fold_batch, rnamc_centroid_fold_batch_multi,
  *    rnamc_bpp_batch_sparse, rnamc_bpp_batch_sparse_multi, rnamc_window_plan, rnamc_bpp_windowed,
- *    rnamc_bpp_windowed_multi, rnamc_mutant_plan, rnamc_mutant_scan, rnamc_mutant_scan_multi */
+ *    rnamc_bpp_windowed_multi, rnamc_mutant_plan, rnamc_mutant_scan, rnamc_mutant_scan_multi,
+ *    rnamc_bpp_alignment, rnamc_bpp_alignment_multi */
 #define RNAMC_ABI_VERSION 3u
 
 /* Compile-time limits.  In the reference these are constants of rna-ss-params
@@ -823,6 +824,63 @@ int rnamc_mutant_scan_multi(rnamc_pool* pool, const uint8_t* bases, uint32_t n, 
                             const uint32_t* positions, uint32_t n_positions, float* log_partition,
                             int64_t* pair_dist2_q, float* max_dp, uint32_t* max_i, uint32_t* max_j,
                             float* paired_prob, float* wt_log_partition, float* wt_paired_prob);
+
+/* ------------------------------------------------------------------------- */
+/* Alignment folding (what CentroidAlifold, PETfold and RNAalifold -p start from): every row of a
+ * multiple alignment is folded without its gaps, its pair probabilities are mapped onto alignment
+ * COLUMNS and averaged over the rows, and the consensus structure is the gamma-centroid fold of the
+ * averaged matrix.  The rows' triangles never reach the host.
+ *   rows          n_rows rows of n_cols bytes, row-major: code 0..3 a base, 4 a gap (PSEUDO_BASE,
+ *                 src/utils.rs:122: what align_char2base makes of every character outside ACGUacgu);
+ *                 1 <= n_rows <= 65535, 1 <= n_cols <= 65535
+ *   Records: row s without its gaps is record s, of n_s bases; map_s[k] is the column of its k-th
+ *   base.  Every record is folded exactly as rnamc_bpp_batch_constrained folds this list of records
+ *   with no constraint strings and the same max_bp_span (counted in the row's own bases, 0 = none),
+ *   flags and summation mode.
+ *   Accumulation is exact and order-free (the rule of rnamc_bpp_windowed).  Every present cell
+ *   (p > -0.5, i < j) of record s contributes the integer q = min(rint((double)p * 2^44), 2^45) (to
+ *   nearest, ties to even) to a signed 64-bit sum of column pair (map_s[i], map_s[j]), and 1 to that
+ *   cell's 32-bit counter of rows in which the pair was present.  Integer adds commute, and at most
+ *   65535 rows keep the sum below 2^61: no output bit depends on the order of rows, groups, streams
+ *   or devices.
+ *   bpp           one packed diagonal-major triangle of n_cols (n_cols + 1) / 2 f32, cell (ci, cj) at
+ *                 rnamc_bpp_index(n_cols, ci, cj) (may be NULL):
+ *                   avg = (float)((double)sum / ((double)n_rows * 2^44))   (int64 -> double to nearest)
+ *                 where the counter is non-zero, -1.0f elsewhere and on the main diagonal.  The
+ *                 denominator is the number of ROWS: a row with a gap in either column contributes
+ *                 zero, as in the tools named above.
+ *   col_paired    n_cols f32 (may be NULL): for column c the sum over the finished triangle in
+ *                 rnamc_bpp_batch_sparse's order: start from +0; for d = 1 .. n_cols-1 ascending add
+ *                 avg(c, c+d) if c + d < n_cols and the cell is present, then avg(c-d, c) if c >= d
+ *                 and the cell is present; one rounded f32 add each, not clamped.
+ *   centroid_thresholds / n_thresholds   0 .. 65535 gammas (0: no consensus folds)
+ *   structs       n_thresholds rows of n_cols bytes '(' ')' '.', row g at structs + g * n_cols
+ *   n_pairs, expect_accuracy   n_thresholds entries each
+ *                 For each g the row, the count and expect_accuracy are exactly what rnamc_centroid_fold
+ *                 returns for the averaged triangle this same call produced (whether or not `bpp` is
+ *                 given); the push order of the pairs is not part of this entry.
+ *   log_partition n_rows f32: ln Z of every record;  row_len  n_rows u32: n_s
+ * Every output pointer may be NULL, except that structs, n_pairs or expect_accuracy with
+ * n_thresholds == 0 is RNAMC_ERR_INVALID_ARG.  Also RNAMC_ERR_INVALID_ARG: a NULL ctx / pool / rows,
+ * n_rows or n_cols 0 or above 65535, thresholds counted but not given.  RNAMC_ERR_INVALID_BASE for a
+ * code above 4, RNAMC_ERR_EMPTY_SEQ for a row with no base (the row is named in rnamc_last_error()).
+ * All of these before any device work.  RNAMC_ERR_OOM when the accumulators and the result (16 bytes
+ * per column-pair cell) do not fit the device.  Results do not depend on grouping, on the group
+ * knobs or on the number of devices. */
+int rnamc_bpp_alignment(rnamc_ctx* ctx, uint32_t n_rows, uint32_t n_cols, const uint8_t* rows,
+                        uint32_t max_bp_span, int uses_contra_model, int allows_short_hairpins,
+                        const float* centroid_thresholds, uint32_t n_thresholds, float* bpp,
+                        float* col_paired, uint8_t* structs, uint32_t* n_pairs, float* expect_accuracy,
+                        float* log_partition, uint32_t* row_len);
+/* The same over the pool's devices: the rows are cut into shards (rnamc_shard_plan over their
+ * ungapped lengths), each context accumulates its shard, the shards' integer sums and counters are
+ * added on the host, and the pool's first context averages and folds: bit-identical to the
+ * single-context entry. */
+int rnamc_bpp_alignment_multi(rnamc_pool* pool, uint32_t n_rows, uint32_t n_cols, const uint8_t* rows,
+                              uint32_t max_bp_span, int uses_contra_model, int allows_short_hairpins,
+                              const float* centroid_thresholds, uint32_t n_thresholds, float* bpp,
+                              float* col_paired, uint8_t* structs, uint32_t* n_pairs,
+                              float* expect_accuracy, float* log_partition, uint32_t* row_len);
 
 #ifdef __cplusplus
 }

@@ -36,6 +36,7 @@ SYMBOLS = [
     "rnamc_bpp_batch_sparse", "rnamc_bpp_batch_sparse_multi",
     "rnamc_window_plan", "rnamc_bpp_windowed", "rnamc_bpp_windowed_multi",
     "rnamc_mutant_plan", "rnamc_mutant_scan", "rnamc_mutant_scan_multi",
+    "rnamc_bpp_alignment", "rnamc_bpp_alignment_multi",
 ]
 
 
@@ -196,6 +197,11 @@ def lib():
     L.rnamc_mutant_scan.argtypes = [vp, vp, C.c_uint32, C.c_char_p, C.c_uint32, C.c_int, C.c_int, vp, C.c_uint32,
                                     vp, vp, vp, vp, vp, vp, vp, vp]
     L.rnamc_mutant_scan_multi.argtypes = L.rnamc_mutant_scan.argtypes
+    # (ctx or pool, n_rows, n_cols, rows, max_bp_span, contra, short hairpins, thresholds, n_thresholds, bpp,
+    # col_paired, structs, n_pairs, expect_accuracy, log_partition, row_len)
+    L.rnamc_bpp_alignment.argtypes = [vp, C.c_uint32, C.c_uint32, vp, C.c_uint32, C.c_int, C.c_int, vp, C.c_uint32,
+                                      vp, vp, vp, vp, vp, vp, vp]
+    L.rnamc_bpp_alignment_multi.argtypes = L.rnamc_bpp_alignment.argtypes
     _lib = L
     return L
 

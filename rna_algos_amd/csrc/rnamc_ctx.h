@@ -317,6 +317,14 @@ struct rnamc_ctx {
   rnamc::DevBuf<float> wn_band, wn_paired;
   rnamc::EventRing wn_events;  // profiling: a pair around every run of window kernels
   int64_t window_chunk_nt = 64ll << 20;
+  // rnamc_bpp_alignment (grow-only): the call's row descriptors and column maps, its integer
+  // accumulators and the averaged triangle (packed diagonal-major over the columns: 16 bytes per
+  // column-pair cell in all), and the column profile
+  rnamc::DevBuf<rnamc::AlignItem> al_items;
+  rnamc::DevBuf<uint32_t> al_maps;
+  rnamc::DevBuf<int64_t> al_sum;
+  rnamc::DevBuf<uint32_t> al_cnt;
+  rnamc::DevBuf<float> al_out, al_paired;
   // rnamc_mutant_scan (grow-only): the wild type's triangle and paired probabilities, kept for the
   // whole call; a chunk's descriptors for the compare and the paired kernel; the call's accumulators
   // (one sum and one max key per mutant) and a chunk's paired probabilities ([record * n + x]).

@@ -192,6 +192,23 @@ void launch_window_finalize(const WindowGeom& g, const int64_t* sum, const uint3
 void launch_window_paired(const WindowGeom& g, const int64_t* sum, const uint32_t* cnt, float* paired,
                           hipStream_t st);
 
+// alignment folding (rnamc_align.hip): the triangles of a group of alignment
+// rows, each of its own length, summed as integers into the column-pair accumulators of the call
+struct AlignItem {
+  uint64_t bpp_off;  // float offset of the row's bpp triangle in `bpp`
+  uint64_t map_off;  // offset of its column map (u32 per base: the column of base k) in `maps`
+  uint32_t n;        // its bases
+  uint32_t pad_;
+};
+// at most 65535 items a launch; max_n: the longest of the launch's items.  sum, cnt and the result
+// are packed diagonal-major triangles over the n_cols columns (rnamc_bpp_index)
+void launch_align_accumulate(const AlignItem* items, uint32_t n_items, uint32_t max_n, const float* bpp,
+                             const uint32_t* maps, uint32_t n_cols, int64_t* sum, uint32_t* cnt, hipStream_t st);
+void launch_align_finalize(uint32_t n_cols, uint32_t n_rows, const int64_t* sum, const uint32_t* cnt, float* out,
+                           hipStream_t st);
+void launch_align_paired(uint32_t n_cols, uint32_t n_rows, const int64_t* sum, const uint32_t* cnt, float* paired,
+                         hipStream_t st);
+
 // point-mutation scan (rnamc_mutant.hip): the triangles of a group of mutants, all
 // of length n, against the wild type's resident triangle
 struct MutantItem {

@@ -265,6 +265,34 @@ inline uint32_t waves_of(int cus, uint64_t items, uint32_t gmax) {
   return static_cast<uint32_t>((w + 3) / 4 * 4);
 }
 
+// The centroid stage of rnamc_centroid_fold_batch and rnamc_bpp_alignment (rnamc_entries_centroid.cpp):
+// the gamma-centroid folds of `count` device-resident triangles (longest first) for every threshold,
+// the (max,+) fill and the traceback on the device in chunks of "centroid_chunk_bytes" of the
+// context's workspace.  Runs on own_stream and drains it.  emit(x, g, row, n_pairs, accuracy) is
+// called once per (sequence x, threshold g) from the calling thread; row == nullptr: the empty fold
+// (every byte '.').  The host scratch lives in the stage and is reused from group to group.
+struct CentroidSeq {
+  uint64_t bpp_off;  // float offset of the sequence's triangle in `d_bpp`
+  uint32_t n;
+};
+using CentroidEmit = std::function<void(uint32_t x, uint32_t g, const uint8_t* row, uint32_t n_pairs, float accuracy)>;
+struct CentroidStage {
+  const char* who = "";
+  int cus = 0;
+  uint64_t launches = 0;  // of all runs so far
+  int init(rnamc_ctx* c, const char* entry);
+  int run(rnamc_ctx* c, const float* d_bpp, const CentroidSeq* seqs, uint32_t count, const float* gammas,
+          uint32_t ng, const CentroidEmit& emit);
+
+ private:
+  std::vector<CentroidItem> items;
+  std::vector<uint32_t> item_seq;  // sequence of every item of the running chunk
+  std::vector<uint64_t> ids;       // the items that need the fill: sequence * ng + threshold
+  std::vector<uint8_t> h_rows;
+  std::vector<uint32_t> h_np;
+  std::vector<float> h_acc;
+};
+
 }  // namespace rnamc
 
 #endif

@@ -86,6 +86,139 @@ int rnamc_centroid_fold_multi(rnamc_ctx* c, const float* bpp_packed, uint32_t n,
 
 namespace rnamc {
 
+int CentroidStage::init(rnamc_ctx* c, const char* entry) {
+  who = entry;
+  HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
+  return RNAMC_OK;
+}
+
+int CentroidStage::run(rnamc_ctx* c, const float* d_bpp, const CentroidSeq* seqs, uint32_t count,
+                       const float* gammas, uint32_t ng, const CentroidEmit& emit) {
+  hipStream_t st = c->own_stream;
+  uint64_t budget = c->ws_floats;
+  if (c->centroid_chunk_bytes > 0)
+    budget = std::min<uint64_t>(budget, static_cast<uint64_t>(c->centroid_chunk_bytes) / 4);
+  // Exact shortcut: with p_max the sequence's largest probability, fl(g * p_max) - 1 <= 0 makes every
+  // pair candidate ((0 + g*p) - 1) <= 0 (rounding is monotone), so by induction over the diagonals
+  // every M stays 0: the fold is empty, its accuracy +0.  p_max comes from the device triangle; such
+  // items (every threshold <= 1 of the reference's grid unless a probability rounds above 1) are
+  // answered here and never reach the fill.
+  try {
+    items.clear();
+    for (uint32_t x = 0; x < count; x++) {
+      CentroidItem it{};
+      it.bpp_off = seqs[x].bpp_off;
+      it.n = seqs[x].n;
+      items.push_back(it);
+    }
+    h_acc.resize(count);
+    ids.clear();
+  } catch (const std::exception&) {
+    set_last_error(std::string(who) + ": no host memory for a group");
+    return RNAMC_ERR_OOM;
+  }
+  HIPCHK(c->cf_acc.grow(count));
+  HIPCHK(c->cf_items.upload(items.data(), count, st));
+  launch_centroid_pmax(c->cf_items, d_bpp, c->cf_acc, count, st);
+  launches++;
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(h_acc.data(), c->cf_acc, count * sizeof(float), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  try {
+    for (uint32_t x = 0; x < count; x++) {
+      const float p_max = h_acc[x];
+      for (uint32_t gi = 0; gi < ng; gi++) {
+        const float g = gammas[gi];
+        const float prod = g * p_max;
+        const float cand = prod - 1.f;
+        const bool empty = !std::isnan(g) && (!(p_max >= -0.5f) || cand <= 0.f);
+        if (!empty) {
+          ids.push_back(static_cast<uint64_t>(x) * ng + gi);
+          continue;
+        }
+        emit(x, gi, nullptr, 0u, 0.f);
+      }
+    }
+  } catch (const std::exception&) {
+    set_last_error(std::string(who) + ": no host memory for a group");
+    return RNAMC_ERR_OOM;
+  }
+  const uint64_t total_items = ids.size();
+  uint64_t done = 0;
+  while (done < total_items) {
+    // items in (sequence, threshold) order: longest sequence first
+    try {
+      items.clear();
+      item_seq.clear();
+      uint64_t m_floats = 0, row_bytes = 0;
+      while (done + items.size() < total_items && items.size() < 65535u) {
+        const uint64_t id = ids[done + items.size()];
+        const uint32_t x = static_cast<uint32_t>(id / ng);
+        const uint64_t need = centroid_item_floats(seqs[x].n);
+        if (!items.empty() && m_floats + need > budget) break;
+        CentroidItem it{};
+        it.m_off = m_floats;
+        it.bpp_off = seqs[x].bpp_off;
+        it.row_off = row_bytes;
+        it.n = seqs[x].n;
+        it.gamma = gammas[id % ng];
+        items.push_back(it);
+        item_seq.push_back(x);
+        m_floats += need;
+        row_bytes += seqs[x].n;
+      }
+      h_rows.resize(row_bytes);
+      h_np.resize(items.size());
+      h_acc.resize(items.size());
+    } catch (const std::exception&) {
+      set_last_error(std::string(who) + ": no host memory for a chunk");
+      return RNAMC_ERR_OOM;
+    }
+    const uint32_t ni = static_cast<uint32_t>(items.size());
+    const uint32_t cmax = items[0].n;
+    const uint64_t row_bytes = h_rows.size();
+    const uint32_t waves = waves_of(cus, ni, cmax);
+    HIPCHK(c->cf_np.grow(ni));
+    HIPCHK(c->cf_acc.grow(ni));
+    HIPCHK(c->sm_rows.grow(row_bytes));
+    HIPCHK(c->sm_stack.grow(static_cast<uint64_t>(waves) * (cmax + 1ull)));
+    HIPCHK(c->cf_items.upload(items.data(), ni, st));
+    CentroidChunk a{};
+    a.items = c->cf_items;
+    a.bpp = d_bpp;
+    a.m = c->d_ws;
+    a.rows = c->sm_rows;
+    a.n_pairs = c->cf_np;
+    a.expect_accuracy = c->cf_acc;
+    a.stack = c->sm_stack;
+    a.n_items = ni;
+    a.stack_cap = cmax + 1u;
+    launch_centroid_batch_init(a, cmax, st);
+    uint32_t active = ni;  // items with n > d: a prefix that only shrinks
+    for (uint32_t d = 1; d < cmax; d++) {
+      while (active > 0 && items[active - 1].n <= d) active--;
+      launch_centroid_batch(a, d, active, cmax, st);
+    }
+    launch_centroid_trace(a, waves, st);
+    launches += cmax + 1ull;
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(h_rows.data(), c->sm_rows, row_bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(h_np.data(), c->cf_np, ni * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(h_acc.data(), c->cf_acc, ni * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (uint32_t x = 0; x < ni; x++) {
+      if (h_np[x] == 0xffffffffu) {
+        set_last_error(std::string(who) + ": traceback stack overflow");
+        return RNAMC_ERR_HIP;
+      }
+      emit(item_seq[x], static_cast<uint32_t>(ids[done + x] % ng), h_rows.data() + items[x].row_off, h_np[x],
+           h_acc[x]);
+    }
+    done += ni;
+  }
+  return RNAMC_OK;
+}
+
 // rnamc_centroid_fold_batch behind both of its entries: the bpp sweep of the context's summation
 // mode, group by group, and per group the centroid stage (rnamc_centroid_batch.hip) on the group's
 // device-resident triangles before the next group reuses the workspace.  Sequence s writes its rows
@@ -101,159 +234,41 @@ int centroid_fold_batch_core(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* bases
   if (int rc = cons.prepare(n_seqs, offsets, constraints, max_bp_span)) return rc;
   StagedCall sc(c, false);
   if (int rc = sc.stage(c, "rnamc_centroid_fold_batch", n_seqs, bases, offsets, cons)) return rc;
-  std::vector<CentroidItem> items;
-  std::vector<uint32_t> item_desc;  // descriptor of every item of the running chunk
-  std::vector<uint64_t> ids;        // the running group's items that need the fill: (descriptor - first) * ng + threshold
-  std::vector<uint8_t> h_rows;
-  std::vector<uint32_t> h_np;
-  std::vector<float> h_acc, h_logz;
+  CentroidStage stage;
+  if (int rc = stage.init(c, "rnamc_centroid_fold_batch")) return rc;
+  std::vector<CentroidSeq> seqs;
+  std::vector<float> h_logz;
   try {  // nothing may throw across the C boundary
     h_logz.resize(n_seqs);
   } catch (const std::exception&) {
     set_last_error("rnamc_centroid_fold_batch: no host memory");
     return RNAMC_ERR_OOM;
   }
-  int cus = 0;
-  HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
   hipStream_t st = c->own_stream;  // (a call with hooks never takes the two-stream route of the tree order)
-  uint64_t launches = 0;  // (run_batch* resets the context's statistics when it starts)
   GroupHooks hooks;
   // (the group's triangles stay on the device, at group-local offsets)
   hooks.before = [&](size_t g, float** out_base) -> int { return group_triangles(c, g, out_base); };
   hooks.after = [&](size_t, uint32_t first, uint32_t count) -> int {
     // the group's sweep and finalize kernel are enqueued on `st`: its DP workspace is dead, the
     // (max,+) triangles of a chunk of items live there
-    uint64_t budget = c->ws_floats;
-    if (c->centroid_chunk_bytes > 0)
-      budget = std::min<uint64_t>(budget, static_cast<uint64_t>(c->centroid_chunk_bytes) / 4);
-    // Exact shortcut: with p_max the sequence's largest probability, fl(g * p_max) - 1 <= 0 makes every
-    // pair candidate ((0 + g*p) - 1) <= 0 (rounding is monotone), so by induction over the diagonals
-    // every M stays 0: the fold is empty, its accuracy +0.  p_max comes from the device triangle; such
-    // items (every threshold <= 1 of the reference's grid unless a probability rounds above 1) are
-    // answered here and never reach the fill.
     try {
-      items.clear();
-      for (uint32_t x = first; x < first + count; x++) {
-        CentroidItem it{};
-        it.bpp_off = c->descs[x].out_off;
-        it.n = c->descs[x].n;
-        items.push_back(it);
-      }
-      h_acc.resize(count);
-      ids.clear();
+      seqs.clear();
+      for (uint32_t x = first; x < first + count; x++) seqs.push_back(CentroidSeq{c->descs[x].out_off, c->descs[x].n});
     } catch (const std::exception&) {
       set_last_error("rnamc_centroid_fold_batch: no host memory for a group");
       return RNAMC_ERR_OOM;
     }
-    HIPCHK(c->cf_acc.grow(count));
-    HIPCHK(c->cf_items.upload(items.data(), count, st));
-    launch_centroid_pmax(c->cf_items, c->st_out[0], c->cf_acc, count, st);
-    launches++;
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(h_acc.data(), c->cf_acc, count * sizeof(float), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    try {
-      for (uint32_t x = 0; x < count; x++) {
-        const SeqDesc& sd = c->descs[first + x];
-        const float p_max = h_acc[x];
-        for (uint32_t gi = 0; gi < ng; gi++) {
-          const float g = gammas[gi];
-          const float prod = g * p_max;
-          const float cand = prod - 1.f;
-          const bool empty = !std::isnan(g) && (!(p_max >= -0.5f) || cand <= 0.f);
-          if (!empty) {
-            ids.push_back(static_cast<uint64_t>(x) * ng + gi);
-            continue;
-          }
-          const uint64_t s = sd.batch_idx;
-          std::memset(structs + struct_offs[s] + static_cast<uint64_t>(gi) * sd.n, '.', sd.n);
-          const uint64_t r = static_cast<uint64_t>(res_idx[s]) * ng + gi;
-          if (n_pairs) n_pairs[r] = 0;
-          if (expect_accuracy) expect_accuracy[r] = 0.f;
-        }
-      }
-    } catch (const std::exception&) {
-      set_last_error("rnamc_centroid_fold_batch: no host memory for a group");
-      return RNAMC_ERR_OOM;
-    }
-    const uint64_t total_items = ids.size();
-    uint64_t done = 0;
-    while (done < total_items) {
-      // items in (descriptor, threshold) order: longest sequence first
-      try {
-        items.clear();
-        item_desc.clear();
-        uint64_t m_floats = 0, row_bytes = 0;
-        while (done + items.size() < total_items && items.size() < 65535u) {
-          const uint64_t id = ids[done + items.size()];
-          const uint32_t x = first + static_cast<uint32_t>(id / ng);
-          const SeqDesc& sd = c->descs[x];
-          const uint64_t need = centroid_item_floats(sd.n);
-          if (!items.empty() && m_floats + need > budget) break;
-          CentroidItem it{};
-          it.m_off = m_floats;
-          it.bpp_off = sd.out_off;
-          it.row_off = row_bytes;
-          it.n = sd.n;
-          it.gamma = gammas[id % ng];
-          items.push_back(it);
-          item_desc.push_back(x);
-          m_floats += need;
-          row_bytes += sd.n;
-        }
-        h_rows.resize(row_bytes);
-        h_np.resize(items.size());
-        h_acc.resize(items.size());
-      } catch (const std::exception&) {
-        set_last_error("rnamc_centroid_fold_batch: no host memory for a chunk");
-        return RNAMC_ERR_OOM;
-      }
-      const uint32_t ni = static_cast<uint32_t>(items.size());
-      const uint32_t cmax = items[0].n;
-      const uint64_t row_bytes = h_rows.size();
-      const uint32_t waves = waves_of(cus, ni, cmax);
-      HIPCHK(c->cf_np.grow(ni));
-      HIPCHK(c->cf_acc.grow(ni));
-      HIPCHK(c->sm_rows.grow(row_bytes));
-      HIPCHK(c->sm_stack.grow(static_cast<uint64_t>(waves) * (cmax + 1ull)));
-      HIPCHK(c->cf_items.upload(items.data(), ni, st));
-      CentroidChunk a{};
-      a.items = c->cf_items;
-      a.bpp = c->st_out[0];
-      a.m = c->d_ws;
-      a.rows = c->sm_rows;
-      a.n_pairs = c->cf_np;
-      a.expect_accuracy = c->cf_acc;
-      a.stack = c->sm_stack;
-      a.n_items = ni;
-      a.stack_cap = cmax + 1u;
-      launch_centroid_batch_init(a, cmax, st);
-      uint32_t active = ni;  // items with n > d: a prefix that only shrinks
-      for (uint32_t d = 1; d < cmax; d++) {
-        while (active > 0 && items[active - 1].n <= d) active--;
-        launch_centroid_batch(a, d, active, cmax, st);
-      }
-      launch_centroid_trace(a, waves, st);
-      launches += cmax + 1ull;
-      HIPCHK(hipGetLastError());
-      HIPCHK(hipMemcpyAsync(h_rows.data(), c->sm_rows, row_bytes, hipMemcpyDeviceToHost, st));
-      HIPCHK(hipMemcpyAsync(h_np.data(), c->cf_np, ni * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-      HIPCHK(hipMemcpyAsync(h_acc.data(), c->cf_acc, ni * sizeof(float), hipMemcpyDeviceToHost, st));
-      HIPCHK(hipStreamSynchronize(st));
-      for (uint32_t x = 0; x < ni; x++) {
-        if (h_np[x] == 0xffffffffu) {
-          set_last_error("rnamc_centroid_fold_batch: traceback stack overflow");
-          return RNAMC_ERR_HIP;
-        }
-        const SeqDesc& sd = c->descs[item_desc[x]];
-        const uint64_t s = sd.batch_idx, gi = ids[done + x] % ng;
-        std::memcpy(structs + struct_offs[s] + gi * sd.n, h_rows.data() + items[x].row_off, sd.n);
-        const uint64_t r = static_cast<uint64_t>(res_idx[s]) * ng + gi;
-        if (n_pairs) n_pairs[r] = h_np[x];
-        if (expect_accuracy) expect_accuracy[r] = h_acc[x];
-      }
-      done += ni;
-    }
+    const int rc = stage.run(c, c->st_out[0], seqs.data(), count, gammas, ng,
+                             [&](uint32_t x, uint32_t gi, const uint8_t* row, uint32_t np, float acc) {
+                               const SeqDesc& sd = c->descs[first + x];
+                               const uint64_t s = sd.batch_idx;
+                               uint8_t* to = structs + struct_offs[s] + static_cast<uint64_t>(gi) * sd.n;
+                               if (row) std::memcpy(to, row, sd.n); else std::memset(to, '.', sd.n);
+                               const uint64_t r = static_cast<uint64_t>(res_idx[s]) * ng + gi;
+                               if (n_pairs) n_pairs[r] = np;
+                               if (expect_accuracy) expect_accuracy[r] = acc;
+                             });
+    if (rc) return rc;
     if (bpp) {
       for (uint32_t x = first; x < first + count; x++) {
         const SeqDesc& sd = c->descs[x];
@@ -266,7 +281,7 @@ int centroid_fold_batch_core(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* bases
   };
   int rc = run_batch_mode(c, n_seqs, c->st_bases, sc.doff.data(), uses_contra_model != 0,
                           allows_short_hairpins != 0, nullptr, nullptr, c->st_logz, st, sc.opts, &hooks);
-  c->stats.launches_other += launches;
+  c->stats.launches_other += stage.launches;
   rc = sc.finish(c, rc, n_seqs, log_partition ? h_logz.data() : nullptr);
   if (rc) return rc;
   if (log_partition)

@@ -77,6 +77,36 @@ int bpp_windowed_fetch(rnamc_ctx* c, const WindowPlan& wp, int64_t* sum, uint32_
 int bpp_windowed_finish(rnamc_ctx* c, const WindowPlan& wp, const int64_t* sum, const uint32_t* cnt,
                         float* band_prob, float* paired_prob);
 
+// rnamc_bpp_alignment behind its two entries (rnamc_entries_align.cpp).  Rows of an alignment cut into
+// records: row row_idx[s] without its gaps is record s, bases [offsets[s], offsets[s + 1]) (offsets[0]
+// = 0); maps is laid out like bases and holds the column of every base.  The single-context entry
+// holds all rows in order, a pool's shard some of them.
+struct AlignRows {
+  uint32_t n_cols = 0;
+  std::vector<uint8_t> bases;
+  std::vector<uint64_t> offsets;
+  std::vector<uint32_t> maps;
+  std::vector<uint32_t> row_idx;
+};
+// every check of the entry that needs no context: pointers, sizes, the codes of every row (the bad
+// row named in rnamc_last_error); *out = all rows
+int bpp_alignment_check(uint32_t n_rows, uint32_t n_cols, const uint8_t* rows, const float* gammas, uint32_t ng,
+                        const uint8_t* structs, const uint32_t* n_pairs, const float* expect_accuracy,
+                        AlignRows* out);
+// The three below run with c->mu HELD by the caller and the context's device current (the
+// accumulators live in the context from the first of them to the last).
+// zero the context's accumulators and add the rows of `ar` into them group by group;
+// log_partition (may be NULL) is the call's whole array, indexed by row
+int bpp_alignment_accumulate(rnamc_ctx* c, const AlignRows& ar, uint32_t max_bp_span, int uses_contra_model,
+                             int allows_short_hairpins, float* log_partition);
+// the context's accumulators to the host (n_cols (n_cols + 1) / 2 entries each, rnamc_bpp_index)
+int bpp_alignment_fetch(rnamc_ctx* c, uint32_t n_cols, int64_t* sum, uint32_t* cnt);
+// average, column profile and consensus folds, and the copies to the host; sum / cnt: host totals to
+// upload first (both NULL: the context's own accumulators as bpp_alignment_accumulate left them)
+int bpp_alignment_finish(rnamc_ctx* c, uint32_t n_rows, uint32_t n_cols, const int64_t* sum, const uint32_t* cnt,
+                         const float* gammas, uint32_t ng, float* bpp, float* col_paired, uint8_t* structs,
+                         uint32_t* n_pairs, float* expect_accuracy);
+
 // rnamc_mutant_scan behind its two entries (rnamc_entries_mutant.cpp).
 // base code of the rank-th (0 .. 2) mutant of a position whose wild-type base is wt: {0,1,2,3} \ {wt} ascending
 inline uint8_t mutant_base_of(uint8_t wt, uint32_t rank) { return static_cast<uint8_t>(rank + (rank >= wt ? 1u : 0u)); }

@@ -543,6 +543,104 @@ int rnamc_bpp_windowed_multi(rnamc_pool* p, const uint8_t* bases, uint64_t n, co
                                     n_shards > 1 ? shards[0].cnt.data() : nullptr, band_prob, paired_prob);
 }
 
+// rnamc_bpp_alignment over the pool: the rows cut into shards by the plan of rnamc_shard_plan over their
+// ungapped lengths, each context accumulating its shard into its own integer sums and counters; these
+// are added on the host — integer adds, any order — and the pool's first context averages the totals
+// and folds them: the bits of the single-context entry.
+int rnamc_bpp_alignment_multi(rnamc_pool* p, uint32_t n_rows, uint32_t n_cols, const uint8_t* rows,
+                              uint32_t max_bp_span, int uses_contra_model, int allows_short_hairpins,
+                              const float* centroid_thresholds, uint32_t n_thresholds, float* bpp,
+                              float* col_paired, uint8_t* structs, uint32_t* n_pairs, float* expect_accuracy,
+                              float* log_partition, uint32_t* row_len) {
+  if (!p) return RNAMC_ERR_INVALID_ARG;
+  rnamc::AlignRows all;
+  if (int rc = rnamc::bpp_alignment_check(n_rows, n_cols, rows, centroid_thresholds, n_thresholds, structs,
+                                          n_pairs, expect_accuracy, &all))
+    return rc;
+  if (p->ctxs.empty()) return RNAMC_ERR_INVALID_ARG;
+  if (row_len)
+    for (uint32_t s = 0; s < n_rows; s++) row_len[s] = static_cast<uint32_t>(all.offsets[s + 1] - all.offsets[s]);
+  std::lock_guard<std::mutex> lock(p->mu);
+  const uint32_t n_shards = static_cast<uint32_t>(std::min<size_t>(p->ctxs.size(), n_rows));
+  const uint64_t cells = rnamc_bpp_len(n_cols);
+  struct Shard {
+    rnamc::AlignRows rows;
+    std::vector<int64_t> sum;
+    std::vector<uint32_t> cnt;
+    int status = RNAMC_OK;
+    std::string error;
+  };
+  std::vector<Shard> shards(n_shards);
+  try {  // nothing may throw across the C boundary
+    if (n_shards > 1) {
+      std::vector<uint32_t> shard_of(n_rows), order;
+      plan(n_rows, all.offsets.data(), n_shards, shard_of.data(), &order);
+      for (Shard& sh : shards) {
+        sh.rows.n_cols = n_cols;
+        sh.rows.offsets.assign(1, 0);
+        sh.sum.resize(cells);
+        sh.cnt.resize(cells);
+      }
+      for (uint32_t x = 0; x < n_rows; x++) {  // longest first inside every shard
+        const uint32_t s = order[x];
+        rnamc::AlignRows& r = shards[shard_of[s]].rows;
+        r.bases.insert(r.bases.end(), all.bases.begin() + all.offsets[s], all.bases.begin() + all.offsets[s + 1]);
+        r.maps.insert(r.maps.end(), all.maps.begin() + all.offsets[s], all.maps.begin() + all.offsets[s + 1]);
+        r.offsets.push_back(r.bases.size());
+        r.row_idx.push_back(s);
+      }
+    }
+  } catch (const std::exception&) {
+    rnamc::set_last_error("rnamc_bpp_alignment_multi: no host memory");
+    return RNAMC_ERR_OOM;
+  }
+  auto work = [&](uint32_t k) {
+    Shard& sh = shards[k];
+    rnamc_ctx* c = p->ctxs[k];
+    std::unique_lock<std::mutex> ctx_lock(c->mu);
+    rnamc::DeviceGuard guard(c->device);
+    if (!guard.ok) {
+      sh.status = RNAMC_ERR_NO_DEVICE;
+      return;
+    }
+    sh.status = rnamc::bpp_alignment_accumulate(c, n_shards > 1 ? sh.rows : all, max_bp_span, uses_contra_model,
+                                                allows_short_hairpins, log_partition);
+    if (sh.status == RNAMC_OK && n_shards > 1)
+      sh.status = rnamc::bpp_alignment_fetch(c, n_cols, sh.sum.data(), sh.cnt.data());
+    if (sh.status) {
+      sh.error = rnamc_last_error();  // (thread-local: carry it to the caller's thread)
+      (void)hipStreamSynchronize(c->own_stream);
+    }
+  };
+  std::vector<std::thread> pool;
+  for (uint32_t k = 1; k < n_shards; k++) {
+    try {
+      pool.emplace_back(work, k);
+    } catch (...) {  // no thread: this shard runs on the caller's thread below
+      work(k);
+    }
+  }
+  work(0);
+  for (std::thread& t : pool) t.join();
+  for (const Shard& sh : shards)
+    if (sh.status) {
+      rnamc::set_last_error(sh.error);
+      return sh.status;
+    }
+  for (uint32_t k = 1; k < n_shards; k++)
+    for (uint64_t x = 0; x < cells; x++) {
+      shards[0].sum[x] += shards[k].sum[x];
+      shards[0].cnt[x] += shards[k].cnt[x];
+    }
+  rnamc_ctx* c = p->ctxs[0];
+  std::unique_lock<std::mutex> ctx_lock(c->mu);
+  rnamc::DeviceGuard guard(c->device);
+  if (!guard.ok) return RNAMC_ERR_NO_DEVICE;
+  return rnamc::bpp_alignment_finish(c, n_rows, n_cols, n_shards > 1 ? shards[0].sum.data() : nullptr,
+                                     n_shards > 1 ? shards[0].cnt.data() : nullptr, centroid_thresholds,
+                                     n_thresholds, bpp, col_paired, structs, n_pairs, expect_accuracy);
+}
+
 // rnamc_mutant_scan over the pool: the mutant list cut into shards (equal records: contiguous bands of
 // equal size); every context folds the wild type itself and scans its shard straight into the caller's
 // arrays.  Per-mutant integers, nothing summed across devices: the bits of the single-context entry.

@@ -271,6 +271,80 @@ def _bpp_windowed(entry, handle, seq, window, uses_contra_model, allows_short_ha
     return WindowedBpp(out, paired, logz, starts)
 
 
+class ColumnBpp(BppMatrix):
+    """The averaged pair probabilities of an alignment over its COLUMNS: a BppMatrix (packed
+    diagonal-major triangle, absent pairs at -1) whose indices are columns."""
+
+    def to_dict(self, min_prob=0.0):
+        """{(ci, cj): p} of the present column pairs with p >= min_prob."""
+        return {(int(a), int(b)): float(q) for a, b, q in zip(*self.pairs(min_prob))}
+
+    def pairs(self, min_prob=0.0):
+        """(ci, cj, p) arrays of the present column pairs with p >= min_prob, ordered by span, then ci."""
+        n = self.n
+        keep = np.nonzero((self.packed > -0.5) & (self.packed >= np.float32(min_prob)))[0]
+        keep = keep[keep >= n]  # (the main diagonal holds -1 anyway)
+        # diagonal d starts at d n - d (d - 1) / 2: the diagonal of a packed index by searchsorted
+        d_all = np.arange(n + 1, dtype=np.int64)
+        starts = d_all * n - d_all * (d_all - 1) // 2
+        d = np.searchsorted(starts, keep, side="right") - 1
+        i = keep - starts[d]
+        return i.astype(np.int64), (i + d).astype(np.int64), self.packed[keep]
+
+
+class AlignmentBpp:
+    """Result of alignment folding (rnamc_bpp_alignment): `bpp` a ColumnBpp over the alignment's columns
+    (each pair's probability averaged over ALL rows), `col_paired` f32[n_cols], `folds` a list of
+    (dot_bracket over the columns, expect_accuracy), one per gamma, `log_z` f32[n_rows] and `row_len`
+    u32[n_rows] (bases of every row)."""
+
+    def __init__(self, bpp, col_paired, folds, log_z, row_len):
+        self.bpp = bpp
+        self.n_cols = int(len(col_paired))
+        self.col_paired = col_paired
+        self.folds = folds
+        self.log_z = log_z
+        self.row_len = row_len
+
+    def pairs(self, min_prob=0.0):
+        """(ci, cj, p) arrays of the column pairs with averaged probability >= min_prob."""
+        return self.bpp.pairs(min_prob)
+
+
+def _align_rows_arg(rows):
+    rows = np.ascontiguousarray(rows, dtype=np.uint8)
+    if rows.ndim != 2:
+        raise _lib.RnamcError(_lib.ERR_INVALID_ARG, "alignment rows must be a 2-D array (n_rows, n_cols) of codes 0..4")
+    if rows.shape[0] >= 2 ** 32 or rows.shape[1] >= 2 ** 32:
+        raise _lib.RnamcError(_lib.ERR_INVALID_ARG, "alignment too large")
+    return rows
+
+
+def _bpp_alignment(entry, handle, rows, uses_contra_model, allows_short_hairpins, centroid_thresholds, max_bp_span,
+                   return_bpp=True):
+    """rnamc_bpp_alignment / _multi on `handle` -> AlignmentBpp (return_bpp False: .bpp is None)"""
+    rows = _align_rows_arg(rows)
+    n_rows, n_cols = int(rows.shape[0]), int(rows.shape[1])
+    gammas = np.ascontiguousarray(centroid_thresholds, dtype=np.float32).reshape(-1)
+    ng = len(gammas)
+    bpp = np.empty(max(bpp_len(n_cols), 1), dtype=np.float32) if return_bpp else None
+    paired = np.empty(max(n_cols, 1), dtype=np.float32)
+    structs = np.empty(max(ng * n_cols, 1), dtype=np.uint8)
+    npairs = np.zeros(max(ng, 1), dtype=np.uint32)
+    acc = np.zeros(max(ng, 1), dtype=np.float32)
+    logz = np.empty(max(n_rows, 1), dtype=np.float32)
+    row_len = np.zeros(max(n_rows, 1), dtype=np.uint32)
+    _lib.check(entry(handle, n_rows, n_cols, rows.ctypes.data if rows.size else None, _span(max_bp_span),
+                     int(bool(uses_contra_model)), int(bool(allows_short_hairpins)),
+                     gammas.ctypes.data if ng else None, ng, bpp.ctypes.data if return_bpp else None,
+                     paired.ctypes.data, structs.ctypes.data if ng else None, npairs.ctypes.data if ng else None,
+                     acc.ctypes.data if ng else None, logz.ctypes.data, row_len.ctypes.data))
+    block = bytes(structs[:ng * n_cols]).decode()
+    folds = [(block[g * n_cols:(g + 1) * n_cols], acc[g]) for g in range(ng)]
+    return AlignmentBpp(ColumnBpp(n_cols, bpp[:bpp_len(n_cols)]) if return_bpp else None, paired[:n_cols], folds,
+                        logz[:n_rows], row_len[:n_rows])
+
+
 class MutantScan:
     """Result of a point-mutation scan (rnamc_mutant_scan), one entry per mutant m = 3 * idx + rank:
     `pos` (u32) and `base` (u8 code) of the mutant, `log_z` (f32) and `wt_log_z` (float),
@@ -651,6 +725,15 @@ class Context:
         return _bpp_windowed(_lib.lib().rnamc_bpp_windowed, self._h, seq, window, uses_contra_model,
                              allows_short_hairpins, stride, max_bp_span, constraint)
 
+    def bpp_alignment(self, rows, uses_contra_model, allows_short_hairpins, centroid_thresholds=(), max_bp_span=0,
+                      return_bpp=True):
+        """Alignment folding (rnamc_bpp_alignment): `rows` a u8 array (n_rows, n_cols) of codes 0..3 and
+        4 for a gap (utils.read_align); every row folded without its gaps, the pair probabilities
+        averaged per column pair over all rows on the device, one consensus fold per gamma
+        -> AlignmentBpp."""
+        return _bpp_alignment(_lib.lib().rnamc_bpp_alignment, self._h, rows, uses_contra_model,
+                              allows_short_hairpins, centroid_thresholds, max_bp_span, return_bpp)
+
     def mutant_scan(self, seq, uses_contra_model, allows_short_hairpins, positions=None, constraint=None,
                     max_bp_span=0):
         """Point-mutation scan of one sequence (rnamc_mutant_scan): every single-base mutant of
@@ -756,6 +839,13 @@ class Pool:
         return _bpp_windowed(_lib.lib().rnamc_bpp_windowed_multi, self._h, seq, window, uses_contra_model,
                              allows_short_hairpins, stride, max_bp_span, constraint)
 
+
+    def bpp_alignment(self, rows, uses_contra_model, allows_short_hairpins, centroid_thresholds=(), max_bp_span=0,
+                      return_bpp=True):
+        """As Context.bpp_alignment, the rows sharded over the pool's contexts
+        (rnamc_bpp_alignment_multi): the same bits."""
+        return _bpp_alignment(_lib.lib().rnamc_bpp_alignment_multi, self._h, rows, uses_contra_model,
+                              allows_short_hairpins, centroid_thresholds, max_bp_span, return_bpp)
 
     def mutant_scan(self, seq, uses_contra_model, allows_short_hairpins, positions=None, constraint=None,
                     max_bp_span=0):
@@ -901,6 +991,18 @@ def mutant_scan(seq, uses_contra_model, allows_short_hairpins, fold_score_sets, 
     with _ctx_lock:
         return _pool_for(fold_score_sets).mutant_scan(seq, uses_contra_model, allows_short_hairpins, positions,
                                                       constraint, max_bp_span)
+
+
+def alignment_fold(rows, uses_contra_model, allows_short_hairpins, fold_score_sets, centroid_thresholds=(),
+                   max_bp_span=0):
+    """Alignment folding (CentroidAlifold / PETfold / RNAalifold -p): every row of the alignment `rows`
+    (u8 (n_rows, n_cols), codes 0..3 and 4 for a gap: utils.read_align) folded without its gaps over
+    the process's devices, the pair probabilities mapped onto columns and averaged over all rows on the
+    device, and the gamma-centroid fold of the averaged matrix for every gamma -> AlignmentBpp.  The
+    rows' triangles stay on the device; the result is one triangle over the columns."""
+    with _ctx_lock:
+        return _pool_for(fold_score_sets).bpp_alignment(rows, uses_contra_model, allows_short_hairpins,
+                                                        centroid_thresholds, max_bp_span)
 
 
 def structure_score(seq, dot_bracket, uses_contra_model, allows_short_hairpins, fold_score_sets):

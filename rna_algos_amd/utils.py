@@ -91,6 +91,124 @@ def read_fasta_raw(path):
     return recs
 
 
+# ---- alignment readers (src/utils.rs:657-754) ----
+# The reference returns (Cols, SeqIds), the alignment column by column; here `rows` is the u8 array
+# (n_rows, n_cols) of the same codes and `rows.T` its Cols.  Lines are cut as BufRead::lines cuts
+# them ('\n', a trailing '\r' dropped), fields as split_whitespace does.
+
+_ALIGN_CODES = np.full(256, PSEUDO_BASE, dtype=np.uint8)
+for _ch, _code in (("A", A), ("C", C_), ("G", G), ("U", U)):
+    _ALIGN_CODES[ord(_ch)] = _ALIGN_CODES[ord(_ch.lower())] = _code
+
+
+def align_char2base(x):
+    """One alignment character (str, bytes of length 1, or its code) -> 0..3 for ACGUacgu, PSEUDO_BASE
+    (4, the gap) for everything else: '-', '.', 'T', 'N', ... (src/utils.rs:746-754)."""
+    if isinstance(x, (str, bytes)):
+        if len(x) != 1:
+            raise ValueError("align_char2base takes one character")
+        x = ord(x)
+    x = int(x)
+    return int(_ALIGN_CODES[x]) if 0 <= x < 256 else PSEUDO_BASE
+
+
+def _align_lines(path):
+    with open(path, "rb") as fh:
+        data = fh.read().decode("utf-8")
+    lines = data.split("\n")
+    if lines and lines[-1] == "":
+        lines.pop()
+    return [ln[:-1] if ln.endswith("\r") else ln for ln in lines]
+
+
+def _align_rows(seqs, what):
+    """equal-length strings -> u8 (n_rows, n_cols); ValueError for ragged rows or none"""
+    if not seqs:
+        raise ValueError(f"{what}: no sequence")
+    n = len(seqs[0])
+    for s, x in enumerate(seqs):
+        if len(x) != n:
+            raise ValueError(f"{what}: row {s} has {len(x)} columns, row 0 has {n}")
+    rows = np.empty((len(seqs), n), dtype=np.uint8)
+    for s, x in enumerate(seqs):
+        codes = np.array([ord(ch) for ch in x], dtype=np.int64)
+        rows[s] = np.where(codes < 256, _ALIGN_CODES[np.minimum(codes, 255)], PSEUDO_BASE)
+    return rows
+
+
+def read_align_clustal(path):
+    """src/utils.rs:657-692: the first line (the CLUSTAL header), empty lines and lines that start with
+    a blank (the conservation line) separate blocks; every other line is `id sequence`, the ids are
+    taken from the first block, later blocks extend the rows in order -> (rows, seq_ids)."""
+    seqs, seq_ids = [], []
+    seq_pointer, has_read_seq_ids = 0, False
+    for i, line in enumerate(_align_lines(path)):
+        if i == 0 or line == "" or line.startswith(" "):
+            if seqs:
+                seq_pointer = 0
+                has_read_seq_ids = True
+            continue
+        fields = line.split()
+        if len(fields) < 2:
+            raise ValueError(f"{path}: line {i + 1}: expected `id sequence`")
+        if not has_read_seq_ids:
+            seq_ids.append(fields[0])
+            seqs.append("")
+        if seq_pointer >= len(seqs):
+            raise ValueError(f"{path}: line {i + 1}: a block with more rows than the first")
+        seqs[seq_pointer] += fields[1]
+        seq_pointer += 1
+    return _align_rows(seqs, path), seq_ids
+
+
+def read_align_fasta(path):
+    """src/utils.rs:694-717: records split at '>', the first whitespace-separated token the id, the
+    rest joined to the row -> (rows, seq_ids)."""
+    seqs, seq_ids = [], []
+    with open(path, "rb") as fh:
+        chunks = fh.read().decode("utf-8").split(">")
+    for i, chunk in enumerate(chunks):
+        if i == 0:
+            continue
+        fields = chunk.split()
+        if not fields:
+            raise ValueError(f"{path}: record {i - 1} has no id")
+        seq_ids.append(fields[0])
+        seqs.append("".join(fields[1:]))
+    return _align_rows(seqs, path), seq_ids
+
+
+def read_align_stockholm(path):
+    """src/utils.rs:719-744: empty lines and lines that start with '#' (the header, #=GF, #=GC, ...)
+    are skipped, reading stops at the first line that starts with '//'; every other line is
+    `id sequence`, one row each (no interleaved blocks) -> (rows, seq_ids)."""
+    seqs, seq_ids = [], []
+    for i, line in enumerate(_align_lines(path)):
+        if line == "" or line.startswith("#"):
+            continue
+        if line.startswith("//"):
+            break
+        fields = line.split()
+        if len(fields) < 2:
+            raise ValueError(f"{path}: line {i + 1}: expected `id sequence`")
+        seq_ids.append(fields[0])
+        seqs.append(fields[1])
+    return _align_rows(seqs, path), seq_ids
+
+
+_ALIGN_READERS = {".aln": read_align_clustal, ".fa": read_align_fasta, ".fasta": read_align_fasta,
+                  ".sto": read_align_stockholm, ".stk": read_align_stockholm}
+
+
+def read_align(path):
+    """The reader of the file's extension: .aln Clustal, .fa / .fasta FASTA, .sto / .stk Stockholm
+    -> (rows, seq_ids)."""
+    ext = os.path.splitext(os.fspath(path))[1].lower()
+    if ext not in _ALIGN_READERS:
+        raise ValueError(f"{path}: unknown alignment format (known: {' '.join(sorted(_ALIGN_READERS))})")
+    return _ALIGN_READERS[ext](path)
+
+
 class FoldScoreSets:
     """`FoldScoreSets::new(init_val)` then `.transfer()` as every reference caller
     does (tests/tests.rs:21-22, src/bin/mccaskill_algo.rs:59-60)."""
