@@ -461,15 +461,18 @@ int rnamc_oracle_bpp_masked(const rnamc_params* p, const uint8_t* seq, uint32_t 
  * (caller-allocated, entries may be NULL), in the struct's order: sums_external,
  * sums_rightmost_basepairs_external, sums_rightmost_basepairs_multibranch, sums_close,
  * sums_accessible, sums_multibranch, sums_1ormore_basepairs.  The sparse maps are dense here with
- * -inf for an absent key (value-preserving: SURVEY 8a N3). */
-int rnamc_oracle_fold_sums(const rnamc_params* p, const uint8_t* seq, uint32_t n,
-                           int uses_contra_model, int allows_short_hairpins, float** mats) {
+ * -inf for an absent key (value-preserving: SURVEY 8a N3).  `mask` as rnamc_oracle_bpp_masked
+ * (both inside passes honour ostate.mask); rnamc_oracle_fold_sums is the call with none. */
+int rnamc_oracle_fold_sums_masked(const rnamc_params* p, const uint8_t* seq, uint32_t n,
+                                  int uses_contra_model, int allows_short_hairpins,
+                                  const uint8_t* mask, float** mats) {
   int st = check_args(p, seq, n);
   if (st) return st;
   if (!mats) return RNAMC_ERR_INVALID_ARG;
   ostate s;
   st = ostate_init(&s, n);
   if (st) return st;
+  s.mask = mask;
   if (uses_contra_model)
     o_get_fold_sums_contra(p, seq, &s, allows_short_hairpins);
   else
@@ -485,6 +488,61 @@ int rnamc_oracle_fold_sums(const rnamc_params* p, const uint8_t* seq, uint32_t n
     if (mats[m])
       for (size_t x = 0; x < (size_t)n * n; x++) mats[m][x] = (float)src[m][x];
   ostate_free(&s);
+  return RNAMC_OK;
+}
+
+int rnamc_oracle_fold_sums(const rnamc_params* p, const uint8_t* seq, uint32_t n,
+                           int uses_contra_model, int allows_short_hairpins, float** mats) {
+  return rnamc_oracle_fold_sums_masked(p, seq, n, uses_contra_model, allows_short_hairpins, NULL,
+                                       mats);
+}
+
+/* The loop scores around one closing pair (i, j), straight from oracle_scoring.h (no DP): what a
+ * top-down walk of the inside grammar reads at C(i, j) and at the E / R cell that opened (i, j).
+ *   scores3[0..2]  hairpin (NaN where the CONTRAfold inside pass scores none: j - i - 1 >
+ *                  RNAMC_MAX_LOOP_LEN), multibranch close, accessible;
+ *   twoloop        the 2-loop scores of the inner pairs (k, l) = (i + 1 + a, j - 1 - b) over
+ *                  a + b <= L = min(RNAMC_MAX_2LOOP_LEN, j - i - 3), a ascending, then b ascending
+ *                  (l descending: the inside pass's own visiting order), (L + 1)(L + 2) / 2 entries
+ *                  (none when j - i < 3); NaN where (k, l) is not a canonical pair, which the
+ *                  inside pass never scores.
+ * Whether (i, j) or (k, l) is a key of sums_close is the caller's business (the fold sums say). */
+int rnamc_oracle_cell_scores(const rnamc_params* p, const uint8_t* seq, uint32_t n,
+                             int uses_contra_model, int allows_short_hairpins, uint32_t i, uint32_t j,
+                             float* scores3, float* twoloop, uint32_t twoloop_cap,
+                             uint32_t* twoloop_count) {
+  int st = check_args(p, seq, n);
+  if (st) return st;
+  (void)allows_short_hairpins; /* decides which pairs are keys, not what a loop scores */
+  if (!scores3 || !(i < j) || j >= n) return RNAMC_ERR_INVALID_ARG;
+  if (!uses_contra_model && j - i + 1 < RNAMC_MIN_SPAN_HAIRPIN_CLOSE) return RNAMC_ERR_INVALID_ARG;
+  const uint32_t L = j - i < 3 ? 0 : (j - i - 3 < RNAMC_MAX_2LOOP_LEN ? j - i - 3 : RNAMC_MAX_2LOOP_LEN);
+  const uint32_t count = j - i < 3 ? 0 : (L + 1) * (L + 2) / 2;
+  if (twoloop_count) *twoloop_count = count;
+  if (twoloop && twoloop_cap < count) return RNAMC_ERR_INVALID_ARG;
+  if (uses_contra_model) {
+    const rnamc_fold_score_sets* f = &p->contra;
+    scores3[0] = j - i - 1 <= RNAMC_MAX_LOOP_LEN ? (float)o_get_hairpin_score_contra(f, seq, i, j) : NAN;
+    scores3[1] = (float)o_get_multibranch_close_score_contra(f, seq, n, i, j);
+    scores3[2] = (float)o_get_accessible_score_contra(f, seq, n, i, j);
+  } else {
+    const rnamc_turner_scores* t = &p->turner;
+    scores3[0] = (float)o_get_hairpin_score(t, seq, i, j);
+    scores3[1] = (float)o_get_multibranch_close_score(t, seq, i, j);
+    scores3[2] = (float)o_get_accessible_score(t, seq, n, i, j);
+  }
+  if (!twoloop) return RNAMC_OK;
+  uint32_t o = 0;
+  for (uint32_t a = 0; a <= L && count; a++)
+    for (uint32_t b = 0; a + b <= L; b++, o++) {
+      const uint32_t k = i + 1 + a, l = j - 1 - b;
+      if (!o_has_canonical_basepair(seq[k], seq[l]))
+        twoloop[o] = NAN;
+      else if (uses_contra_model)
+        twoloop[o] = (float)o_get_2loop_score_contra(&p->contra, seq, i, j, k, l);
+      else
+        twoloop[o] = (float)o_get_2loop_score(&p->turner, seq, i, j, k, l);
+    }
   return RNAMC_OK;
 }
 

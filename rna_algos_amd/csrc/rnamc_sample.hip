@@ -14,8 +14,8 @@
 //
 // Decision rule (bit-reproducible): candidates in a fixed order, 64 per wave step.  Pass 0: max.
 // Pass 1: total = sum of exp(term - max), as a running sum of per-step inclusive wave scans.
-// Pass 2: the first candidate whose inclusive prefix (the same sums) exceeds u * total; if
-// rounding leaves none, the last candidate with nonzero weight.  Decisions of at most 512
+// Pass 2: the first candidate of nonzero weight whose inclusive prefix (the same sums) exceeds
+// u * total; if rounding leaves none, the last candidate with nonzero weight.  Decisions of at most 512
 // candidates (every C cell: <= 498) keep their terms in registers; longer ones re-evaluate.
 //
 // Layout: one wave per (sequence, sample) pair, a grid-stride loop over the group's pairs; the
@@ -103,12 +103,15 @@ __device__ int decide(const S& sm, uint32_t type, uint32_t i, uint32_t j, uint32
     for (uint32_t st = 0; st < steps; st++) step_total(st, val(st));
   }
   const float target = u * run;
-  // pass 2: first inclusive prefix above the target
+  // pass 2: first inclusive prefix above the target.  The scan's prefixes are sums in different
+  // orders and need not be monotone in f32: a candidate of weight 0 (a -inf term) can round above
+  // its predecessor and above a target that lies between them, so only nonzero weights may hit.
   float run2 = 0.f;
   int pick = -1;
   auto step_pick = [&](uint32_t st, float v) {
-    const float p = run2 + wave_scan(weight(v), lane);
-    const uint64_t hit = ballot64(p > target);
+    const float w = weight(v);
+    const float p = run2 + wave_scan(w, lane);
+    const uint64_t hit = ballot64(p > target && w > 0.f);
     if (hit) pick = static_cast<int>(st * 64u + static_cast<uint32_t>(__ffsll(static_cast<long long>(hit)) - 1));
     run2 = __shfl(p, 63, 64);
   };

@@ -26,6 +26,9 @@ def lib():
         L.rnamc_oracle_bpp.argtypes = [vp, vp, C.c_uint32, C.c_int, C.c_int, vp, vp]
         L.rnamc_oracle_bpp_dump.argtypes = [vp, vp, C.c_uint32, C.c_int, C.c_int, vp, vp, vp]
         L.rnamc_oracle_fold_sums.argtypes = [vp, vp, C.c_uint32, C.c_int, C.c_int, vp]
+        L.rnamc_oracle_fold_sums_masked.argtypes = [vp, vp, C.c_uint32, C.c_int, C.c_int, vp, vp]
+        L.rnamc_oracle_cell_scores.argtypes = [vp, vp, C.c_uint32, C.c_int, C.c_int, C.c_uint32,
+                                               C.c_uint32, vp, vp, C.c_uint32, vp]
         L.rnamc_oracle_bpp_batch.argtypes = [vp, C.c_uint32, vp, vp, C.c_int, C.c_int, vp, vp, vp,
                                              C.c_uint32]
         L.rnamc_oracle_exact_bpp.argtypes = [vp, vp, C.c_uint32, C.c_int, C.c_int, vp, vp]
@@ -151,6 +154,44 @@ def fold_sums(params_ptr, seq, contra, short=False):
     ptrs = (C.c_void_p * 7)(*[m.ctypes.data for m in mats])
     _chk(lib().rnamc_oracle_fold_sums(params_ptr, seq.ctypes.data, n, int(contra), int(short), ptrs))
     return dict(zip(FOLD_SUMS_FIELDS, mats))
+
+
+def fold_sums_masked(params_ptr, seq, contra, short=False, mask=None):
+    """fold_sums with the sums_close keys of the masked pairs absent (mask as bpp_masked)"""
+    seq = np.ascontiguousarray(seq, dtype=np.uint8)
+    n = seq.shape[0]
+    keep, mptr = _mask_arg(mask, n)
+    mats = [np.empty((n, n), dtype=np.float32) for _ in range(7)]
+    ptrs = (C.c_void_p * 7)(*[m.ctypes.data for m in mats])
+    _chk(lib().rnamc_oracle_fold_sums_masked(params_ptr, seq.ctypes.data, n, int(contra), int(short),
+                                             mptr, ptrs))
+    del keep
+    return dict(zip(FOLD_SUMS_FIELDS, mats))
+
+
+MAX_2LOOP_LEN = 30
+
+
+def twoloop_slots(i, j):
+    """the (a, b) of cell_scores' 2-loop list of the closing pair (i, j), in its order"""
+    if j - i < 3:
+        return []
+    L = min(MAX_2LOOP_LEN, j - i - 3)
+    return [(a, b) for a in range(L + 1) for b in range(L + 1 - a)]
+
+
+def cell_scores(params_ptr, seq, contra, short, i, j):
+    """Loop scores around the closing pair (i, j), straight from oracle_scoring.h -> (hairpin (NaN
+    where the CONTRAfold pass scores none), multibranch close, accessible as np.float32, f32 array
+    of the 2-loop scores in the order of twoloop_slots, NaN where the inner pair is not canonical)"""
+    seq = np.ascontiguousarray(seq, dtype=np.uint8)
+    three = np.empty(3, dtype=np.float32)
+    tl = np.empty((MAX_2LOOP_LEN + 1) * (MAX_2LOOP_LEN + 2) // 2, dtype=np.float32)
+    count = C.c_uint32()
+    _chk(lib().rnamc_oracle_cell_scores(params_ptr, seq.ctypes.data, seq.shape[0], int(contra),
+                                        int(short), int(i), int(j), three.ctypes.data, tl.ctypes.data,
+                                        tl.shape[0], C.byref(count)))
+    return three[0], three[1], three[2], tl[:count.value].copy()
 
 
 def bpp_batch(params_ptr, seqs, contra, short=False, n_threads=1, want_bpp=True):
