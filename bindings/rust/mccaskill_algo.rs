@@ -62,6 +62,8 @@ extern "C" {
   fn rnamc_bpp_len(n: u32) -> u64;
   fn rnamc_bpp_batch_multi(pool: *mut RnamcPool, n_seqs: u32, bases: *const u8, offsets: *const u64, uses_contra_model: c_int, allows_short_hairpins: c_int, bpp: *mut f32, out_offsets: *const u64, log_partition: *mut f32) -> c_int;
   fn rnamc_bpp_batch_sparse_multi(pool: *mut RnamcPool, n_seqs: u32, bases: *const u8, offsets: *const u64, constraints: *const c_char, max_bp_span: u32, uses_contra_model: c_int, allows_short_hairpins: c_int, min_prob: f32, pair_start: *mut u64, pair_count: *mut u64, pair_i: *mut u32, pair_j: *mut u32, pair_prob: *mut f32, pairs_cap: u64, pairs_total: *mut u64, paired_prob: *mut f32, log_partition: *mut f32) -> c_int;
+  fn rnamc_context_profile_batch(ctx: *mut RnamcCtx, n_seqs: u32, bases: *const u8, offsets: *const u64, constraints: *const c_char, max_bp_span: u32, uses_contra_model: c_int, allows_short_hairpins: c_int, profile: *mut f32, log_partition: *mut f32) -> c_int;
+  fn rnamc_context_profile_batch_multi(pool: *mut RnamcPool, n_seqs: u32, bases: *const u8, offsets: *const u64, constraints: *const c_char, max_bp_span: u32, uses_contra_model: c_int, allows_short_hairpins: c_int, profile: *mut f32, log_partition: *mut f32) -> c_int;
   fn rnamc_window_plan(n: u64, window: u32, stride: u32, max_bp_span: u32, n_windows: *mut u64, band: *mut u32, starts: *mut u64, starts_cap: u64) -> c_int;
   fn rnamc_bpp_windowed(ctx: *mut RnamcCtx, bases: *const u8, n: u64, constraint: *const c_char, window: u32, stride: u32, max_bp_span: u32, uses_contra_model: c_int, allows_short_hairpins: c_int, band_prob: *mut f32, paired_prob: *mut f32, window_log_partition: *mut f32) -> c_int;
   fn rnamc_bpp_alignment(ctx: *mut RnamcCtx, n_rows: u32, n_cols: u32, rows: *const u8, max_bp_span: u32, uses_contra_model: c_int, allows_short_hairpins: c_int, centroid_thresholds: *const f32, n_thresholds: u32, bpp: *mut f32, col_paired: *mut f32, structs: *mut u8, n_pairs: *mut u32, expect_accuracy: *mut f32, log_partition: *mut f32, row_len: *mut u32) -> c_int;

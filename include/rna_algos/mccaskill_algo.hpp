@@ -283,6 +283,22 @@ std::vector<SparseProbMat<T>> mccaskill_algo_batch_sparse(const Context& ctx, co
   return out;
 }
 
+// Structural context profiles (rnamc_context_profile_batch; CapR's profile): per record six rows of
+// n floats, row-major, in the order bulge, exterior, hairpin, internal, multibranch, stem.
+inline std::vector<std::vector<float>> context_profile_batch(const Context& ctx, const std::vector<Seq>& seqs,
+                                                             bool uses_contra_model, bool allows_short_hairpins) {
+  std::vector<uint64_t> off(seqs.size() + 1, 0);
+  for (size_t s = 0; s < seqs.size(); s++) off[s + 1] = off[s] + seqs[s].size();
+  std::vector<Base> bases(off.back());
+  for (size_t s = 0; s < seqs.size(); s++) std::copy(seqs[s].begin(), seqs[s].end(), bases.begin() + off[s]);
+  std::vector<float> prof(6 * off.back() + 1);
+  check(rnamc_context_profile_batch(ctx.get(), static_cast<uint32_t>(seqs.size()), bases.data(), off.data(), nullptr,
+                                    0, uses_contra_model, allows_short_hairpins, prof.data(), nullptr));
+  std::vector<std::vector<float>> out(seqs.size());
+  for (size_t s = 0; s < seqs.size(); s++) out[s].assign(prof.begin() + 6 * off[s], prof.begin() + 6 * off[s + 1]);
+  return out;
+}
+
 // Windowed local folding of one sequence of any length below 2^31 (rnamc_bpp_windowed; no counterpart
 // in the reference): every window of `window` bases (starts 0, stride, 2 stride, ..., and a last window
 // ending at the sequence's end) folded with max_bp_span (0: no limit), each pair's probability averaged

@@ -43,7 +43,8 @@ extern "C" {
  *    rnamc_constraint_check, rnamc_centroid_fold_batch, rnamc_centroid_fold_batch_multi,
  *    rnamc_bpp_batch_sparse, rnamc_bpp_batch_sparse_multi, rnamc_window_plan, rnamc_bpp_windowed,
  *    rnamc_bpp_windowed_multi, rnamc_mutant_plan, rnamc_mutant_scan, rnamc_mutant_scan_multi,
- *    rnamc_bpp_alignment, rnamc_bpp_alignment_multi */
+ *    rnamc_bpp_alignment, rnamc_bpp_alignment_multi, rnamc_context_profile_batch,
+ *    rnamc_context_profile_batch_multi, rnamc_context_profile_stats */
 #define RNAMC_ABI_VERSION 3u
 
 /* Compile-time limits.  In the reference these are constants of rna-ss-params
@@ -694,6 +695,43 @@ int rnamc_bpp_batch_sparse_multi(rnamc_pool* pool, uint32_t n_seqs, const uint8_
                                  uint64_t* pair_count, uint32_t* pair_i, uint32_t* pair_j,
                                  float* pair_prob, uint64_t pairs_cap, uint64_t* pairs_total,
                                  float* paired_prob, float* log_partition);
+
+/* ------------------------------------------------------------------------- */
+/* Structural context profiles (CapR's profile): for every base u of every record six probabilities
+ * over the Boltzmann ensemble of the model's structure space (what rnamc_structure_score scores as
+ * finite, minus the pairs that constraints remove), computed on the device off the matrices of the
+ * inside-outside sweep.  Rows, in CapR's order:
+ *   0 bulge        u unpaired in a 2-loop with exactly one empty side
+ *   1 exterior     u unpaired and enclosed by no pair
+ *   2 hairpin      u unpaired, the innermost enclosing pair closes a hairpin
+ *   3 internal     u unpaired in a 2-loop with both sides non-empty
+ *   4 multibranch  u unpaired, the innermost enclosing pair closes a loop with >= 2 branches
+ *   5 stem         u paired: rnamc_bpp_batch_sparse's paired_prob, bit for bit
+ *   bases, offsets, constraints, max_bp_span, flags   as rnamc_bpp_batch_constrained
+ *   profile       record s at profile + 6 * (offsets[s] - offsets[0]): six rows of n_s f32 (never NULL)
+ *   log_partition n_seqs f32 (may be NULL)
+ * The sweep always runs in the reference's summation order, whatever "summation_mode" says.  Rows 0,
+ * 2, 3 and 4 are sums of 64-bit integers of 2^-44 (every loop's probability rounded once), so every
+ * output bit is independent of grouping, the other records of the batch, knobs, devices and runs;
+ * the six rows sum to 1 up to the f32 logsumexp arithmetic of the sweep (a few 1e-4).  No triangle
+ * reaches the host.  RNAMC_ERR_INVALID_ARG for a NULL ctx / pool or a NULL profile; bad records and
+ * bad constraints fail before any device work. */
+int rnamc_context_profile_batch(rnamc_ctx* ctx, uint32_t n_seqs, const uint8_t* bases,
+                                const uint64_t* offsets, const char* constraints, uint32_t max_bp_span,
+                                int uses_contra_model, int allows_short_hairpins, float* profile,
+                                float* log_partition);
+/* The same over the pool's devices: the shards of rnamc_shard_plan, each through its own context,
+ * written straight into the caller's arrays. */
+int rnamc_context_profile_batch_multi(rnamc_pool* pool, uint32_t n_seqs, const uint8_t* bases,
+                                      const uint64_t* offsets, const char* constraints,
+                                      uint32_t max_bp_span, int uses_contra_model,
+                                      int allows_short_hairpins, float* profile, float* log_partition);
+/* Statistics of the context's last rnamc_context_profile_batch, beside rnamc_ctx_stats (whose block
+ * keeps its size): the launches of the entry's own kernels (the copy of sums_multibranch between the
+ * two sweeps, the profile kernels, the paired kernel; also counted in launches_other) and, when
+ * profiling is on, the summed device time of those behind the sweep in milliseconds (0 otherwise).
+ * Both 0 when the context's last call was another entry. */
+int rnamc_context_profile_stats(rnamc_ctx* ctx, uint64_t* launches_context, double* ms_context);
 
 /* ------------------------------------------------------------------------- */
 /* Windowed local folding of ONE long sequence (what RNAplfold and LocalFold compute): every window

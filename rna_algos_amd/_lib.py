@@ -37,6 +37,7 @@ SYMBOLS = [
     "rnamc_window_plan", "rnamc_bpp_windowed", "rnamc_bpp_windowed_multi",
     "rnamc_mutant_plan", "rnamc_mutant_scan", "rnamc_mutant_scan_multi",
     "rnamc_bpp_alignment", "rnamc_bpp_alignment_multi",
+    "rnamc_context_profile_batch", "rnamc_context_profile_batch_multi", "rnamc_context_profile_stats",
 ]
 
 
@@ -202,6 +203,12 @@ def lib():
     L.rnamc_bpp_alignment.argtypes = [vp, C.c_uint32, C.c_uint32, vp, C.c_uint32, C.c_int, C.c_int, vp, C.c_uint32,
                                       vp, vp, vp, vp, vp, vp, vp]
     L.rnamc_bpp_alignment_multi.argtypes = L.rnamc_bpp_alignment.argtypes
+    # (ctx or pool, n_seqs, bases, offsets, constraints, max_bp_span, contra, short hairpins, profile,
+    # log_partition)
+    L.rnamc_context_profile_batch.argtypes = [vp, C.c_uint32, vp, vp, C.c_char_p, C.c_uint32, C.c_int, C.c_int,
+                                              vp, vp]
+    L.rnamc_context_profile_batch_multi.argtypes = L.rnamc_context_profile_batch.argtypes
+    L.rnamc_context_profile_stats.argtypes = [vp, u64p, C.POINTER(C.c_double)]
     _lib = L
     return L
 

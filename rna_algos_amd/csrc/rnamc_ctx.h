@@ -338,6 +338,14 @@ struct rnamc_ctx {
   rnamc::DevBuf<float> mt_paired;
   rnamc::EventRing mt_events;  // profiling: a pair around every run of mutant kernels
   int64_t mutant_chunk_nt = 64ll << 20;
+  // rnamc_context_profile_batch (grow-only): a group's record descriptors, its copies of
+  // sums_multibranch (taken between the two sweeps), its integer accumulators and staged profiles
+  rnamc::DevBuf<rnamc::ContextItem> cx_items;
+  rnamc::DevBuf<float> cx_qm, cx_out;
+  rnamc::DevBuf<unsigned long long> cx_acc;
+  rnamc::EventRing cx_events;  // profiling: a pair around every group's context kernels
+  uint64_t cx_launches = 0;    // rnamc_context_profile_stats: of the last call (BatchPlan::begin resets them)
+  double cx_ms = 0.0;
 };
 
 namespace rnamc {
@@ -361,6 +369,10 @@ int ensure_ws(rnamc_ctx* c, uint64_t floats);
 struct GroupHooks {
   std::function<int(size_t g, float** out_base)> before;
   std::function<int(size_t g, uint32_t first_desc, uint32_t n_desc)> after;
+  // optional (reference-order sweep with an outside sweep only): between group g's inside and
+  // outside sweeps, everything of the inside sweep enqueued on the sweep's stream and nothing of the
+  // outside sweep on any -- what it enqueues there precedes the first outside launch on either stream
+  std::function<int(size_t g, uint32_t first_desc, uint32_t n_desc)> mid;
 };
 
 // The front the two sweeps share: a batch sorted longest-first and cut greedily into lock-step

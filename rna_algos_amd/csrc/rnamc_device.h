@@ -229,6 +229,37 @@ inline uint32_t mutant_strip_of(uint64_t len) {
 void launch_mutant_compare(const MutantItem* items, uint32_t n_items, const float* wt, const float* bpp, uint32_t n,
                            int64_t* sum, uint64_t* key, hipStream_t st);
 
+// structural context profiles (rnamc_context.hip): per-base loop-type
+// probabilities off the workspace of a reference-order group.  Rows of a record's profile in CapR's
+// order, and the rows of its 64-bit integer accumulators (n + 1 entries each, units of 2^-44: bulge,
+// hairpin and internal as difference arrays, multibranch as per-base sums)
+enum : int { CTX_ROW_BULGE = 0, CTX_ROW_EXTERIOR = 1, CTX_ROW_HAIRPIN = 2, CTX_ROW_INTERNAL = 3, CTX_ROW_MULTI = 4,
+             CTX_ROW_STEM = 5, CTX_ROWS = 6 };
+enum : int { CTX_ACC_BULGE = 0, CTX_ACC_HAIRPIN = 1, CTX_ACC_INTERNAL = 2, CTX_ACC_MULTI = 3, CTX_ACC_ROWS = 4 };
+struct ContextItem {
+  uint64_t qm_off;   // float offset of the record's copy of sums_multibranch in `qm` (tri_pad floats)
+  uint64_t acc_off;  // offset of its CTX_ACC_ROWS * (n + 1) accumulators in `acc`
+  uint64_t out_off;  // float offset of its CTX_ROWS * n profile in `out`
+};
+struct ContextBatch {
+  const SeqDesc* seqs;       // descriptors of the launch's records, longest first
+  const ContextItem* items;  // one per descriptor
+  const uint8_t* bases;
+  float* workspace;
+  const float* bpp;          // the group's finished triangles (SeqDesc::out_off; absent pairs negative)
+  const rnamc_params* params;
+  const float* hp_init;
+  float* qm;
+  unsigned long long* acc;   // zeroed by the caller
+  float* out;
+};
+// at most 65535 records a launch; max_n: the longest of them
+// M_QM of every record into its copy: between the inside and the outside sweep
+void launch_context_save(const ContextBatch& b, uint32_t n_items, uint32_t max_n, hipStream_t st);
+// rows 0 .. 4 of every record's profile: behind the group's finalize kernel -> the number of launches
+uint32_t launch_context_profile(const ContextBatch& b, bool contra, uint32_t n_items, uint32_t max_n,
+                                hipStream_t st);
+
 // ---- tree-order summation mode (rnamc_tree.hip) ----
 // Dense n x n matrices with row stride ld (>= n + 32, a multiple of 32 floats), msz floats
 // each; "row" = [i * ld + j], "col" = [j * ld + i].  The outside sweep reuses four slots.

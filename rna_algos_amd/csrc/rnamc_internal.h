@@ -51,6 +51,15 @@ int bpp_batch_sparse_core(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* bases, c
                           float* paired_prob, float* log_partition);
 int bpp_batch_sparse_finish(uint64_t total, bool wants_lists, uint64_t pairs_cap, uint64_t* pairs_total);
 
+// rnamc_context_profile_batch behind its two entries (rnamc_entries_context.cpp): the arguments of
+// the entry after context_profile_check, plus where sequence s writes — its six rows at profile +
+// prof_offs[s], its log partition at index res_idx[s]
+int context_profile_check(uint32_t n_seqs, const uint8_t* bases, const uint64_t* offsets, const float* profile);
+int context_profile_core(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* bases, const uint64_t* offsets,
+                         const char* constraints, uint32_t max_bp_span, int uses_contra_model,
+                         int allows_short_hairpins, const uint32_t* res_idx, const uint64_t* prof_offs,
+                         float* profile, float* log_partition);
+
 // rnamc_bpp_windowed behind its two entries (rnamc_entries_window.cpp).  The window list of a call:
 // n_grid windows at 0, stride, 2 stride, ..., and with has_last one more at n - w.
 struct WindowPlan {

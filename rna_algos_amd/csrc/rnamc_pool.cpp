@@ -452,6 +452,93 @@ int rnamc_bpp_batch_sparse_multi(rnamc_pool* p, uint32_t n_seqs, const uint8_t* 
   return rnamc::bpp_batch_sparse_finish(cursor.load(), pair_i != nullptr, pairs_cap, pairs_total);
 }
 
+// rnamc_context_profile_batch over the pool: the same shards, each through its own context; profiles
+// and log partitions go straight into the caller's arrays.
+int rnamc_context_profile_batch_multi(rnamc_pool* p, uint32_t n_seqs, const uint8_t* bases, const uint64_t* offsets,
+                                      const char* constraints, uint32_t max_bp_span, int uses_contra_model,
+                                      int allows_short_hairpins, float* profile, float* log_partition) {
+  if (!p) return RNAMC_ERR_INVALID_ARG;
+  if (int rc = rnamc::context_profile_check(n_seqs, bases, offsets, profile)) return rc;
+  // the whole batch before the pool is read or any device sees a part of it (the span limit needs no check)
+  if (constraints && n_seqs) {
+    std::vector<int32_t> words;
+    for (uint32_t s = 0; s < n_seqs; s++) {
+      const uint32_t n = static_cast<uint32_t>(offsets[s + 1] - offsets[s]);
+      uint32_t bad = 0;
+      const char* why = "";
+      int rc = RNAMC_OK;
+      try {  // nothing may throw across the C boundary
+        words.resize(2ull * n);
+        rc = rnamc::compile_constraint(constraints + (offsets[s] - offsets[0]), n, words.data(), &bad, &why);
+      } catch (const std::exception&) {
+        rnamc::set_last_error("constraints: no host memory");
+        return RNAMC_ERR_OOM;
+      }
+      if (rc) {
+        rnamc::set_last_error("constraint of record " + std::to_string(s) + ", position " +
+                              std::to_string(bad) + ": " + why);
+        return rc;
+      }
+    }
+  }
+  if (p->ctxs.empty()) return RNAMC_ERR_INVALID_ARG;
+  if (n_seqs == 0) return RNAMC_OK;
+  std::lock_guard<std::mutex> lock(p->mu);
+  const uint32_t n_shards = static_cast<uint32_t>(std::min<size_t>(p->ctxs.size(), n_seqs));
+  std::vector<uint32_t> shard_of(n_seqs), order;
+  plan(n_seqs, offsets, n_shards, shard_of.data(), &order);
+  struct Shard {
+    std::vector<uint32_t> members;  // batch indices, longest first
+    std::vector<uint8_t> bases;
+    std::vector<char> cons;
+    std::vector<uint64_t> offsets, prof_offs;
+    int status = RNAMC_OK;
+    std::string error;
+  };
+  std::vector<Shard> shards(n_shards);
+  for (uint32_t x = 0; x < n_seqs; x++) shards[shard_of[order[x]]].members.push_back(order[x]);
+  for (Shard& sh : shards) {
+    uint64_t total = 0;
+    for (uint32_t s : sh.members) total += offsets[s + 1] - offsets[s];
+    sh.bases.resize(total);
+    if (constraints) sh.cons.resize(total);
+    sh.offsets.assign(1, 0);
+    for (uint32_t s : sh.members) {
+      const uint64_t n = offsets[s + 1] - offsets[s];
+      std::memcpy(sh.bases.data() + sh.offsets.back(), bases + offsets[s], n);
+      if (constraints) std::memcpy(sh.cons.data() + sh.offsets.back(), constraints + (offsets[s] - offsets[0]), n);
+      sh.offsets.push_back(sh.offsets.back() + n);
+      sh.prof_offs.push_back(6ull * (offsets[s] - offsets[0]));
+    }
+  }
+  auto work = [&](uint32_t k) {
+    Shard& sh = shards[k];
+    if (sh.members.empty()) return;
+    // (the members themselves are the result indices: the shard writes the caller's arrays)
+    sh.status = rnamc::context_profile_core(
+        p->ctxs[k], static_cast<uint32_t>(sh.members.size()), sh.bases.data(), sh.offsets.data(),
+        constraints ? sh.cons.data() : nullptr, max_bp_span, uses_contra_model, allows_short_hairpins,
+        sh.members.data(), sh.prof_offs.data(), profile, log_partition);
+    if (sh.status) sh.error = rnamc_last_error();  // (thread-local: carry it to the caller's thread)
+  };
+  std::vector<std::thread> pool;
+  for (uint32_t k = 1; k < n_shards; k++) {
+    try {
+      pool.emplace_back(work, k);
+    } catch (...) {  // no thread: this shard runs on the caller's thread below
+      work(k);
+    }
+  }
+  work(0);
+  for (std::thread& t : pool) t.join();
+  for (const Shard& sh : shards)
+    if (sh.status) {
+      rnamc::set_last_error(sh.error);
+      return sh.status;
+    }
+  return RNAMC_OK;
+}
+
 // rnamc_bpp_windowed over the pool: the window list cut into shards (equal windows: contiguous bands of
 // equal size), each context accumulating its shard into its own integer sums and counters; these are added
 // on the host — integer adds, any order — and the pool's first context finalises the totals: the bits of

@@ -41,6 +41,8 @@ namespace rnamc {
 int BatchPlan::begin(rnamc_ctx* ctx, uint32_t n_seqs, const uint64_t* offsets) {
   c = ctx;
   c->stats = rnamc_batch_stats{};
+  c->cx_launches = 0;
+  c->cx_ms = 0.0;
   c->kev_class.clear();
   c->descs.clear();
   c->group_begin.clear();
@@ -360,6 +362,12 @@ int run_batch(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* d_bases, const uint6
         if (pair_next) pairs_done = heads_done = d + 1;
         d += 1;
       }
+    }
+    // (both inside schedules end on `st` alone; the outside schedules order their second stream
+    // behind an event recorded on `st` after this point)
+    if (hooks && hooks->mid && !opts.inside_only) {
+      rc = hooks->mid(g, gb, nseq);
+      if (rc) return rc;
     }
     if (prof) HIPCHK(hipEventRecord(gev[4 * g + 1], st));
     // (rnamc_fold_scores needs the sums_close key set only: no outside sweep; the output

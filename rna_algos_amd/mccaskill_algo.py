@@ -214,6 +214,26 @@ def _bpp_batch_sparse(entry, handle, seqs, uses_contra_model, allows_short_hairp
     return out, logz[:ns]
 
 
+# rows of a structural context profile (rnamc_context_profile_batch), CapR's order
+CONTEXTS = ("bulge", "exterior", "hairpin", "internal", "multibranch", "stem")
+
+
+def _context_profile_batch(entry, handle, seqs, uses_contra_model, allows_short_hairpins, constraints,
+                           max_bp_span):
+    """rnamc_context_profile_batch / _multi on `handle` -> (list of (6, n_s) f32 views, log partition
+    f32[n_seqs])."""
+    lens, offsets, bases = _pack(seqs)
+    cons = _constraint_bytes(constraints, lens)
+    ns = len(seqs)
+    prof = np.zeros(max(6 * int(offsets[-1]), 1), dtype=np.float32)
+    logz = np.empty(max(ns, 1), dtype=np.float32)
+    _lib.check(entry(handle, ns, bases.ctypes.data, offsets.ctypes.data, cons, _span(max_bp_span),
+                     int(bool(uses_contra_model)), int(bool(allows_short_hairpins)), prof.ctypes.data,
+                     logz.ctypes.data))
+    out = [prof[6 * int(offsets[s]):6 * int(offsets[s + 1])].reshape(6, int(lens[s])) for s in range(ns)]
+    return out, logz[:ns]
+
+
 class WindowedBpp:
     """Result of windowed local folding (rnamc_bpp_windowed): `band` is an (N, B) f32 view,
     band[i, d] = the probability of pair (i, i + d) averaged over the windows that contain it (-1:
@@ -572,7 +592,12 @@ class Context:
     def stats(self):
         st = _lib.BatchStats()
         _lib.check(_lib.lib().rnamc_ctx_stats(self._h, C.byref(st), C.sizeof(st), None))
-        return {k: getattr(st, k) for k, _ in st._fields_}
+        out = {k: getattr(st, k) for k, _ in st._fields_}
+        # (rnamc_context_profile_stats: beside the block, whose size is part of the ABI)
+        launches, ms = C.c_uint64(0), C.c_double(0.0)
+        _lib.check(_lib.lib().rnamc_context_profile_stats(self._h, C.byref(launches), C.byref(ms)))
+        out["launches_context"], out["ms_context"] = launches.value, ms.value
+        return out
 
     def bpp_batch(self, seqs, uses_contra_model, allows_short_hairpins, constraints=None,
                   max_bp_span=0):
@@ -717,6 +742,14 @@ class Context:
         return _bpp_batch_sparse(_lib.lib().rnamc_bpp_batch_sparse, self._h, list(seqs), uses_contra_model,
                                  allows_short_hairpins, min_prob, constraints, max_bp_span)
 
+    def context_profile_batch(self, seqs, uses_contra_model, allows_short_hairpins, constraints=None,
+                              max_bp_span=0):
+        """Structural context profiles (rnamc_context_profile_batch): per base the probabilities of
+        CONTEXTS -> (list of (6, n_s) f32 arrays, log partition f32[n_seqs]).
+        constraints, max_bp_span: as bpp_batch."""
+        return _context_profile_batch(_lib.lib().rnamc_context_profile_batch, self._h, list(seqs),
+                                      uses_contra_model, allows_short_hairpins, constraints, max_bp_span)
+
     def bpp_windowed(self, seq, window, uses_contra_model, allows_short_hairpins, stride=1, max_bp_span=0,
                      constraint=None):
         """Windowed local folding of one (long) sequence (rnamc_bpp_windowed): every window of
@@ -831,6 +864,13 @@ class Pool:
         (rnamc_bpp_batch_sparse_multi)."""
         return _bpp_batch_sparse(_lib.lib().rnamc_bpp_batch_sparse_multi, self._h, list(seqs),
                                  uses_contra_model, allows_short_hairpins, min_prob, constraints, max_bp_span)
+
+    def context_profile_batch(self, seqs, uses_contra_model, allows_short_hairpins, constraints=None,
+                              max_bp_span=0):
+        """As Context.context_profile_batch, sharded over the pool's contexts
+        (rnamc_context_profile_batch_multi): the same bits."""
+        return _context_profile_batch(_lib.lib().rnamc_context_profile_batch_multi, self._h, list(seqs),
+                                      uses_contra_model, allows_short_hairpins, constraints, max_bp_span)
 
     def bpp_windowed(self, seq, window, uses_contra_model, allows_short_hairpins, stride=1, max_bp_span=0,
                      constraint=None):
@@ -968,6 +1008,25 @@ def mccaskill_algo_batch_sparse(seqs, uses_contra_model, allows_short_hairpins, 
         return _pool_for(fold_score_sets).bpp_batch_sparse(list(seqs), uses_contra_model,
                                                            allows_short_hairpins, min_prob, constraints,
                                                            max_bp_span)
+
+
+def context_profile_batch(seqs, uses_contra_model, allows_short_hairpins, fold_score_sets, constraints=None,
+                          max_bp_span=0):
+    """Structural context profiles (CapR's profile) of every sequence over the process's devices:
+    profiles[s] is a (6, n_s) f32 array whose rows are the probabilities that base u is unpaired in
+    a bulge, the exterior loop, a hairpin, an internal loop or a multibranch loop, or is paired
+    (CONTEXTS) -> (profiles, log partition f32[n_seqs]).  Always the reference's summation order."""
+    with _ctx_lock:
+        return _pool_for(fold_score_sets).context_profile_batch(list(seqs), uses_contra_model,
+                                                                allows_short_hairpins, constraints, max_bp_span)
+
+
+def context_profile(seq, uses_contra_model, allows_short_hairpins, fold_score_sets, constraint=None,
+                    max_bp_span=0):
+    """context_profile_batch of one record -> ((6, n) f32 array, log partition)."""
+    prof, logz = context_profile_batch([seq], uses_contra_model, allows_short_hairpins, fold_score_sets,
+                                       None if constraint is None else [constraint], max_bp_span)
+    return prof[0], float(logz[0])
 
 
 def mccaskill_algo_windowed(seq, window, uses_contra_model, allows_short_hairpins, fold_score_sets,
