@@ -244,7 +244,9 @@ int rnamc_ctx_set_params(rnamc_ctx* ctx, const rnamc_params* params);
  * Tuning (all optional): "group_max_seqs","group_max_nt","group_ws_bytes","block_threads",
  * "fuse_inside","dual_outside","dual_min_cells","dual_max_diag","order_inside","order_outside",
  * "latency_mode","lat_max_cells","lat_inside","lat_e_waves","lat_pairs",
- * "lat_merge","lat_zr_ahead","profile"; tree-order mode: "tree_two" (two anti-diagonals per
+ * "lat_merge","lat_zr_ahead","lat_split" (latency forms of the outside sweep: probs_multibranch and
+ * the multibranch half of the pair probabilities as two launches per diagonal, the 2-loop half beside
+ * them on the second stream; default 0),"profile"; tree-order mode: "tree_two" (two anti-diagonals per
  * launch, default 1), "tree_tpc" (threads per cell: 64 / 128 / 256 / 1024, 0 = by diagonal size),
  * "tree_band" (width of a band of anti-diagonals whose cubic products take their mid-field from
  * the tiled kernel k_tree_mid one band ahead: 0 / 32 / 64 / 96 / 128, default 64; 0 = every launch
@@ -253,7 +255,9 @@ int rnamc_ctx_set_params(rnamc_ctx* ctx, const rnamc_params* params);
  * workgroups of the previous launch, default 1), "tree_waves" (waves a tree-order launch may hold
  * at once when it picks threads per cell, default 5120), "tree_short" (sums of at most this many
  * terms take one wave per cell, default 256), "tree_ahead_waves" (waves up to which the ahead role
- * takes one wave per cell instead of one per row, default 16384), "tree_side_stream" (0: probe
+ * takes one wave per cell instead of one per row, default 16384), "tree_xcd_rows" (1: workgroups of a
+ * sweep launch of at least 64 workgroups a sequence are dealt so that 32 neighbouring rows share an XCD,
+ * grids padded to multiples of 64; default 0; same results), "tree_side_stream" (0: probe
  * whether the side stream runs beside the caller's stream and sweep unbanded if not — the default;
  * 1 / 2: take it as concurrent / serialised without probing), "tree_lane" (lane-per-cell sweeps,
  * rnamc_tree_lane.h: 0 never, 1 for calls of several sequences and at least "tree_lane_min_nt"
@@ -268,6 +272,8 @@ int rnamc_ctx_set_params(rnamc_ctx* ctx, const rnamc_params* params);
  * rnamc_centroid_fold_batch: "centroid_chunk_bytes" (bytes of (max,+) matrices one chunk of
  * (record, threshold) items may take; 0 — the default — = the workspace the context holds for the
  * group; never more than that workspace, never less than one item; results do not depend on it).
+ * rnamc_bpp_windowed / rnamc_mutant_scan: "window_chunk_nt" / "mutant_chunk_nt" (nucleotides one staged
+ * call of theirs takes; described with those entries below).
  * Every knob is per context. */
 int rnamc_ctx_set(rnamc_ctx* ctx, const char* name, int64_t value);
 

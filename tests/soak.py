@@ -1,6 +1,8 @@
 """Randomised soak of the HIP path against the CPU oracle: ragged batches, all three model
 variants, random scheduling knobs.  Test infrastructure, not collected by pytest (minutes
-of oracle time); run on the GPU box:  python tests/soak.py [rounds] [seed]"""
+of oracle time); run on the GPU box:  python tests/soak.py [rounds] [seed]
+The collected, deterministic part is tests/test_gpu_knob_forms.py: every knob drawn here at fixed
+values, every pair of their values in a written-out table, on batches whose oracle result is shared."""
 import os
 import sys
 

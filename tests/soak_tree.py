@@ -6,7 +6,9 @@ rounding of an order-free sum (bounds as in tests/test_gpu_tree.py, |dp| with tw
 identical bits when the same batch is run a second time (deterministic); whether a lone call of
 one member gives the batch's bits is printed (it may take another threads-per-cell variant).
 Test infrastructure, not collected by pytest; run on the GPU box:
-    python tests/soak_tree.py [rounds] [seed]"""
+    python tests/soak_tree.py [rounds] [seed]
+The collected, deterministic part is tests/test_gpu_tree_policy.py (the launch-shape knobs at fixed
+values) beside tests/test_gpu_tree.py (the kernel variants)."""
 import os
 import sys
 

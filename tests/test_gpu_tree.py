@@ -293,13 +293,13 @@ def test_tree_n16384_banded_and_oom(params):
 
 @pytest.mark.parametrize("contra,short", VARIANTS)
 def test_tree_kernel_variants_agree(ctx, params, contra, short):
-    """one / two diagonals per launch, 64 / 256 / 1024 threads per cell: the same sums in other
+    """one / two diagonals per launch, 64 / 128 / 256 / 1024 threads per cell: the same sums in other
     orders — equal to f32 rounding, and each within the bound against the exact evaluation."""
     seqs = [O.splitmix_seq(n, 7 * n) for n in (5, 6, 37, 150, 301, 410)]
     exact = [O.exact_bpp(params.ptr, s, contra, short) for s in seqs]
     base = None
     for two in (1, 0):
-        for tpc in (0, 64, 256, 1024):
+        for tpc in (0, 64, 128, 256, 1024):
             m, z = run(ctx, seqs, contra, short, 1, tree_two=two, tree_tpc=tpc)
             for s, a, za, (xb, xz) in zip(seqs, m, z, exact):
                 same, dt = deviation(a.packed, xb)
