@@ -5,12 +5,14 @@
 #define RNAMC_ENTRIES_H
 
 #include "rnamc_ctx.h"
+#include "rnamc_shards.h"
 
 namespace rnamc {
 
 // Hard constraints of one batch call (include/rnamc.h).  prepare() validates
 // and compiles every record on the host, before any device work and before the context's lock: two
-// words per base, laid out like the staged bases (rnamc_scoring.h, pair_allowed).  A call with
+// words per base, laid out like the staged bases (rnamc_scoring.h, pair_allowed), by the record loop
+// the pool's pre-validation runs too (compile_constraints, rnamc_shards.h).  A call with
 // nothing to constrain (no string or only '.', no span limit below the longest record) is not
 // active: it runs exactly the unconstrained sweep.
 struct ConsCall {
@@ -32,29 +34,9 @@ struct ConsCall {
     try {  // nothing may throw across the C boundary
       words.assign(2 * total, -1);  // (no string: every base free, outside every constraint pair)
     } catch (const std::exception&) {
-      set_last_error("constraints: no host memory");
-      return RNAMC_ERR_OOM;
+      return no_host_memory("constraints");
     }
-    if (!strings) return RNAMC_OK;
-    for (uint32_t s = 0; s < n_seqs; s++) {
-      const uint64_t off = offsets[s] - lo;
-      uint32_t bad = 0;
-      const char* why = "";
-      int rc = RNAMC_OK;
-      try {
-        rc = compile_constraint(strings + off, static_cast<uint32_t>(offsets[s + 1] - offsets[s]),
-                                words.data() + 2 * off, &bad, &why);
-      } catch (const std::exception&) {
-        set_last_error("constraints: no host memory");
-        return RNAMC_ERR_OOM;
-      }
-      if (rc) {
-        set_last_error("constraint of record " + std::to_string(s) + ", position " + std::to_string(bad) +
-                       ": " + why);
-        return rc;
-      }
-    }
-    return RNAMC_OK;
+    return strings ? compile_constraints(n_seqs, offsets, strings, words.data()) : RNAMC_OK;
   }
 };
 

@@ -222,14 +222,13 @@ int CentroidStage::run(rnamc_ctx* c, const float* d_bpp, const CentroidSeq* seqs
 // rnamc_centroid_fold_batch behind both of its entries: the bpp sweep of the context's summation
 // mode, group by group, and per group the centroid stage (rnamc_centroid_batch.hip) on the group's
 // device-resident triangles before the next group reuses the workspace.  Sequence s writes its rows
-// at structs + struct_offs[s] and its per-threshold results at index res_idx[s] * n_thresholds
-// (log_partition at res_idx[s]): the pool's shards address the caller's arrays with them.
+// at structs + n_thresholds * place.base(s) and its per-threshold results at index place.idx(s) *
+// n_thresholds (log_partition at place.idx(s)): the pool's shards address the caller's arrays with them.
 int centroid_fold_batch_core(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* bases, const uint64_t* offsets,
                              const char* constraints, uint32_t max_bp_span, int uses_contra_model,
                              int allows_short_hairpins, const float* gammas, uint32_t ng, uint8_t* structs,
-                             const uint64_t* struct_offs, const uint32_t* res_idx, uint32_t* n_pairs,
-                             float* expect_accuracy, float* log_partition, float* bpp,
-                             const uint64_t* out_offsets) {
+                             const Place& place, uint32_t* n_pairs, float* expect_accuracy,
+                             float* log_partition, float* bpp, const uint64_t* out_offsets) {
   ConsCall cons;
   if (int rc = cons.prepare(n_seqs, offsets, constraints, max_bp_span)) return rc;
   StagedCall sc(c, false);
@@ -261,10 +260,10 @@ int centroid_fold_batch_core(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* bases
     const int rc = stage.run(c, c->st_out[0], seqs.data(), count, gammas, ng,
                              [&](uint32_t x, uint32_t gi, const uint8_t* row, uint32_t np, float acc) {
                                const SeqDesc& sd = c->descs[first + x];
-                               const uint64_t s = sd.batch_idx;
-                               uint8_t* to = structs + struct_offs[s] + static_cast<uint64_t>(gi) * sd.n;
+                               const uint32_t s = sd.batch_idx;
+                               uint8_t* to = structs + ng * place.base(s, offsets) + uint64_t{gi} * sd.n;
                                if (row) std::memcpy(to, row, sd.n); else std::memset(to, '.', sd.n);
-                               const uint64_t r = static_cast<uint64_t>(res_idx[s]) * ng + gi;
+                               const uint64_t r = static_cast<uint64_t>(place.idx(s)) * ng + gi;
                                if (n_pairs) n_pairs[r] = np;
                                if (expect_accuracy) expect_accuracy[r] = acc;
                              });
@@ -285,7 +284,7 @@ int centroid_fold_batch_core(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* bases
   rc = sc.finish(c, rc, n_seqs, log_partition ? h_logz.data() : nullptr);
   if (rc) return rc;
   if (log_partition)
-    for (uint32_t s = 0; s < n_seqs; s++) log_partition[res_idx[s]] = h_logz[s];
+    for (uint32_t s = 0; s < n_seqs; s++) log_partition[place.idx(s)] = h_logz[s];
   return RNAMC_OK;
 }
 
@@ -315,23 +314,9 @@ int rnamc_centroid_fold_batch(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* base
                                          bpp, out_offsets))
     return rc;
   if (n_seqs == 0) return RNAMC_OK;
-  std::vector<uint64_t> struct_offs;
-  std::vector<uint32_t> res_idx;
-  try {  // nothing may throw across the C boundary
-    struct_offs.resize(n_seqs);
-    res_idx.resize(n_seqs);
-  } catch (const std::exception&) {
-    set_last_error("rnamc_centroid_fold_batch: no host memory");
-    return RNAMC_ERR_OOM;
-  }
-  for (uint32_t s = 0; s < n_seqs; s++) {
-    struct_offs[s] = static_cast<uint64_t>(n_thresholds) * (offsets[s] - offsets[0]);
-    res_idx[s] = s;
-  }
   return centroid_fold_batch_core(c, n_seqs, bases, offsets, constraints, max_bp_span, uses_contra_model,
-                                  allows_short_hairpins, centroid_thresholds, n_thresholds, structs,
-                                  struct_offs.data(), res_idx.data(), n_pairs, expect_accuracy, log_partition,
-                                  bpp, out_offsets);
+                                  allows_short_hairpins, centroid_thresholds, n_thresholds, structs, Place(), n_pairs,
+                                  expect_accuracy, log_partition, bpp, out_offsets);
 }
 
 }  // extern "C"

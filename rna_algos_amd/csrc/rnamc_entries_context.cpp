@@ -15,11 +15,10 @@ int context_profile_check(uint32_t n_seqs, const uint8_t* bases, const uint64_t*
 }
 
 // rnamc_context_profile_batch behind both of its entries.  Sequence s writes its six rows at
-// profile + prof_offs[s] and its log partition at index res_idx[s].
+// profile + CTX_ROWS * place.base(s) and its log partition at index place.idx(s).
 int context_profile_core(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* bases, const uint64_t* offsets,
                          const char* constraints, uint32_t max_bp_span, int uses_contra_model,
-                         int allows_short_hairpins, const uint32_t* res_idx, const uint64_t* prof_offs,
-                         float* profile, float* log_partition) {
+                         int allows_short_hairpins, const Place& place, float* profile, float* log_partition) {
   ConsCall cons;
   if (int rc = cons.prepare(n_seqs, offsets, constraints, max_bp_span)) return rc;
   StagedCall sc(c, false);
@@ -130,7 +129,8 @@ int context_profile_core(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* bases, co
     HIPCHK(hipStreamSynchronize(st));
     for (uint32_t x = 0; x < count; x++) {
       const SeqDesc& sd = c->descs[first + x];
-      std::memcpy(profile + prof_offs[sd.batch_idx], h_prof.data() + items[x].out_off,
+      std::memcpy(profile + static_cast<uint64_t>(CTX_ROWS) * place.base(sd.batch_idx, offsets),
+                  h_prof.data() + items[x].out_off,
                   static_cast<uint64_t>(CTX_ROWS) * sd.n * sizeof(float));
     }
     return RNAMC_OK;
@@ -150,7 +150,7 @@ int context_profile_core(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* bases, co
   rc = sc.finish(c, rc, n_seqs, log_partition ? h_logz.data() : nullptr);
   if (rc) return rc;
   if (log_partition)
-    for (uint32_t s = 0; s < n_seqs; s++) log_partition[res_idx[s]] = h_logz[s];
+    for (uint32_t s = 0; s < n_seqs; s++) log_partition[place.idx(s)] = h_logz[s];
   return RNAMC_OK;
 }
 
@@ -164,21 +164,8 @@ int rnamc_context_profile_batch(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* ba
   if (!c) return RNAMC_ERR_INVALID_ARG;
   if (int rc = context_profile_check(n_seqs, bases, offsets, profile)) return rc;
   if (n_seqs == 0) return RNAMC_OK;
-  std::vector<uint64_t> prof_offs;
-  std::vector<uint32_t> res_idx;
-  try {  // nothing may throw across the C boundary
-    prof_offs.resize(n_seqs);
-    res_idx.resize(n_seqs);
-  } catch (const std::exception&) {
-    set_last_error("rnamc_context_profile_batch: no host memory");
-    return RNAMC_ERR_OOM;
-  }
-  for (uint32_t s = 0; s < n_seqs; s++) {
-    prof_offs[s] = static_cast<uint64_t>(CTX_ROWS) * (offsets[s] - offsets[0]);
-    res_idx[s] = s;
-  }
   return context_profile_core(c, n_seqs, bases, offsets, constraints, max_bp_span, uses_contra_model,
-                              allows_short_hairpins, res_idx.data(), prof_offs.data(), profile, log_partition);
+                              allows_short_hairpins, Place(), profile, log_partition);
 }
 
 int rnamc_context_profile_stats(rnamc_ctx* c, uint64_t* launches_context, double* ms_context) {

@@ -27,16 +27,16 @@ int bpp_batch_sparse_check(uint32_t n_seqs, const uint8_t* bases, const uint64_t
 }
 
 // rnamc_bpp_batch_sparse behind both of its entries.  Sequence s writes its count (and start) at
-// index res_idx[s], its log partition there too, its paired probabilities at paired_prob +
-// pp_offs[s]; a group claims its part of the caller's three arrays from `cursor`, which the shards
+// index place.idx(s), its log partition there too, its paired probabilities at paired_prob +
+// place.base(s); a group claims its part of the caller's three arrays from `cursor`, which the shards
 // of a pool share.  A group that does not fit (or a counting call) is counted only; the cursor ends
 // at the total either way and the entry compares it with pairs_cap.
 int bpp_batch_sparse_core(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* bases, const uint64_t* offsets,
                           const char* constraints, uint32_t max_bp_span, int uses_contra_model,
-                          int allows_short_hairpins, float min_prob, const uint32_t* res_idx,
-                          const uint64_t* pp_offs, uint64_t* pair_start, uint64_t* pair_count, uint32_t* pair_i,
-                          uint32_t* pair_j, float* pair_prob, uint64_t pairs_cap, std::atomic<uint64_t>* cursor,
-                          float* paired_prob, float* log_partition) {
+                          int allows_short_hairpins, float min_prob, const Place& place, uint64_t* pair_start,
+                          uint64_t* pair_count, uint32_t* pair_i, uint32_t* pair_j, float* pair_prob,
+                          uint64_t pairs_cap, std::atomic<uint64_t>* cursor, float* paired_prob,
+                          float* log_partition) {
   ConsCall cons;
   if (int rc = cons.prepare(n_seqs, offsets, constraints, max_bp_span)) return rc;
   StagedCall sc(c, false);
@@ -105,7 +105,7 @@ int bpp_batch_sparse_core(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* bases, c
     const uint64_t start = cursor->fetch_add(group_total);
     const bool fill = pair_i != nullptr && start + group_total <= pairs_cap;
     for (uint32_t x = 0; x < count; x++) {
-      const uint32_t r = res_idx[c->descs[first + x].batch_idx];
+      const uint32_t r = place.idx(c->descs[first + x].batch_idx);
       if (pair_count) pair_count[r] = h_totals[x];
       if (fill) pair_start[r] = start + items[x].out_off;
     }
@@ -140,7 +140,8 @@ int bpp_batch_sparse_core(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* bases, c
     if (paired_prob)
       for (uint32_t x = 0; x < count; x++) {
         const SeqDesc& sd = c->descs[first + x];
-        std::memcpy(paired_prob + pp_offs[sd.batch_idx], h_paired.data() + items[x].pp_off, sd.n * sizeof(float));
+        std::memcpy(paired_prob + place.base(sd.batch_idx, offsets), h_paired.data() + items[x].pp_off,
+                    sd.n * sizeof(float));
       }
     return RNAMC_OK;
   };
@@ -150,7 +151,7 @@ int bpp_batch_sparse_core(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* bases, c
   rc = sc.finish(c, rc, n_seqs, log_partition ? h_logz.data() : nullptr);
   if (rc) return rc;
   if (log_partition)
-    for (uint32_t s = 0; s < n_seqs; s++) log_partition[res_idx[s]] = h_logz[s];
+    for (uint32_t s = 0; s < n_seqs; s++) log_partition[place.idx(s)] = h_logz[s];
   return RNAMC_OK;
 }
 
@@ -180,24 +181,10 @@ int rnamc_bpp_batch_sparse(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* bases, 
     return rc;
   *pairs_total = 0;
   if (n_seqs == 0) return RNAMC_OK;
-  std::vector<uint64_t> pp_offs;
-  std::vector<uint32_t> res_idx;
-  try {  // nothing may throw across the C boundary
-    pp_offs.resize(n_seqs);
-    res_idx.resize(n_seqs);
-  } catch (const std::exception&) {
-    set_last_error("rnamc_bpp_batch_sparse: no host memory");
-    return RNAMC_ERR_OOM;
-  }
-  for (uint32_t s = 0; s < n_seqs; s++) {
-    pp_offs[s] = offsets[s] - offsets[0];
-    res_idx[s] = s;
-  }
   std::atomic<uint64_t> cursor{0};
   if (int rc = bpp_batch_sparse_core(c, n_seqs, bases, offsets, constraints, max_bp_span, uses_contra_model,
-                                     allows_short_hairpins, min_prob, res_idx.data(), pp_offs.data(), pair_start,
-                                     pair_count, pair_i, pair_j, pair_prob, pairs_cap, &cursor, paired_prob,
-                                     log_partition))
+                                     allows_short_hairpins, min_prob, Place(), pair_start, pair_count, pair_i,
+                                     pair_j, pair_prob, pairs_cap, &cursor, paired_prob, log_partition))
     return rc;
   return bpp_batch_sparse_finish(cursor.load(), pair_i != nullptr, pairs_cap, pairs_total);
 }

@@ -23,42 +23,52 @@ void hp_init_table(const rnamc_turner_scores& t, uint32_t len, float* out);
 // byte outside the set or an unbalanced bracket, with its position in *bad_pos and the reason in *why.
 int compile_constraint(const char* str, uint32_t n, int32_t* words, uint32_t* bad_pos, const char** why);
 
+// Where the records of a batch core write in the caller's arrays.  The three cores below serve a
+// context entry, whose records are the caller's (the identity: both pointers NULL), and a pool's
+// shard, whose record s is the caller's record res_idx[s] and starts base_off[s] bases into the
+// caller's batch (RecordShards, rnamc_shards.h).  Per-record results go to index idx(s), per-base
+// results to a multiple of base(s, offsets) that the core knows.
+struct Place {
+  const uint32_t* res_idx = nullptr;
+  const uint64_t* base_off = nullptr;
+  uint32_t idx(uint32_t s) const { return res_idx ? res_idx[s] : s; }
+  uint64_t base(uint32_t s, const uint64_t* offsets) const { return base_off ? base_off[s] : offsets[s] - offsets[0]; }
+};
+
 // rnamc_centroid_fold_batch behind its two entries (rnamc_entries_centroid.cpp): the arguments of the entry after
-// centroid_fold_batch_check, plus where sequence s writes — its rows at structs + struct_offs[s], its
-// per-threshold results at index res_idx[s] * n_thresholds, its log partition at res_idx[s]
+// centroid_fold_batch_check, plus where sequence s writes — its rows at structs + n_thresholds * base(s),
+// its per-threshold results at index idx(s) * n_thresholds, its log partition at idx(s)
 int centroid_fold_batch_check(uint32_t n_seqs, const uint8_t* bases, const uint64_t* offsets,
                               const float* gammas, uint32_t ng, const uint8_t* structs, const float* bpp,
                               const uint64_t* out_offsets);
 int centroid_fold_batch_core(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* bases, const uint64_t* offsets,
                              const char* constraints, uint32_t max_bp_span, int uses_contra_model,
                              int allows_short_hairpins, const float* gammas, uint32_t ng, uint8_t* structs,
-                             const uint64_t* struct_offs, const uint32_t* res_idx, uint32_t* n_pairs,
-                             float* expect_accuracy, float* log_partition, float* bpp,
-                             const uint64_t* out_offsets);
+                             const Place& place, uint32_t* n_pairs, float* expect_accuracy,
+                             float* log_partition, float* bpp, const uint64_t* out_offsets);
 
 // rnamc_bpp_batch_sparse behind its two entries (rnamc_entries_sparse.cpp): the arguments of the entry after
 // bpp_batch_sparse_check, plus where sequence s writes — count, start and log partition at index
-// res_idx[s], paired probabilities at paired_prob + pp_offs[s] — and the cursor from which every
+// idx(s), paired probabilities at paired_prob + base(s) — and the cursor from which every
 // group claims its part of the three list arrays (shared by the shards of a pool)
 int bpp_batch_sparse_check(uint32_t n_seqs, const uint8_t* bases, const uint64_t* offsets, float min_prob,
                            const uint64_t* pair_start, const uint64_t* pair_count, const uint32_t* pair_i,
                            const uint32_t* pair_j, const float* pair_prob, const uint64_t* pairs_total);
 int bpp_batch_sparse_core(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* bases, const uint64_t* offsets,
                           const char* constraints, uint32_t max_bp_span, int uses_contra_model,
-                          int allows_short_hairpins, float min_prob, const uint32_t* res_idx,
-                          const uint64_t* pp_offs, uint64_t* pair_start, uint64_t* pair_count, uint32_t* pair_i,
-                          uint32_t* pair_j, float* pair_prob, uint64_t pairs_cap, std::atomic<uint64_t>* cursor,
-                          float* paired_prob, float* log_partition);
+                          int allows_short_hairpins, float min_prob, const Place& place, uint64_t* pair_start,
+                          uint64_t* pair_count, uint32_t* pair_i, uint32_t* pair_j, float* pair_prob,
+                          uint64_t pairs_cap, std::atomic<uint64_t>* cursor, float* paired_prob,
+                          float* log_partition);
 int bpp_batch_sparse_finish(uint64_t total, bool wants_lists, uint64_t pairs_cap, uint64_t* pairs_total);
 
 // rnamc_context_profile_batch behind its two entries (rnamc_entries_context.cpp): the arguments of
 // the entry after context_profile_check, plus where sequence s writes — its six rows at profile +
-// prof_offs[s], its log partition at index res_idx[s]
+// 6 * base(s), its log partition at index idx(s)
 int context_profile_check(uint32_t n_seqs, const uint8_t* bases, const uint64_t* offsets, const float* profile);
 int context_profile_core(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* bases, const uint64_t* offsets,
                          const char* constraints, uint32_t max_bp_span, int uses_contra_model,
-                         int allows_short_hairpins, const uint32_t* res_idx, const uint64_t* prof_offs,
-                         float* profile, float* log_partition);
+                         int allows_short_hairpins, const Place& place, float* profile, float* log_partition);
 
 // rnamc_bpp_windowed behind its two entries (rnamc_entries_window.cpp).  The window list of a call:
 // n_grid windows at 0, stride, 2 stride, ..., and with has_last one more at n - w.
