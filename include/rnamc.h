@@ -44,7 +44,8 @@ extern "C" {
  *    rnamc_bpp_batch_sparse, rnamc_bpp_batch_sparse_multi, rnamc_window_plan, rnamc_bpp_windowed,
  *    rnamc_bpp_windowed_multi, rnamc_mutant_plan, rnamc_mutant_scan, rnamc_mutant_scan_multi,
  *    rnamc_bpp_alignment, rnamc_bpp_alignment_multi, rnamc_context_profile_batch,
- *    rnamc_context_profile_batch_multi, rnamc_context_profile_stats */
+ *    rnamc_context_profile_batch_multi, rnamc_context_profile_stats, rnamc_duplex_batch,
+ *    rnamc_duplex_batch_multi, rnamc_duplex_score */
 #define RNAMC_ABI_VERSION 3u
 
 /* Compile-time limits.  In the reference these are constants of rna-ss-params
@@ -925,6 +926,90 @@ int rnamc_bpp_alignment_multi(rnamc_pool* pool, uint32_t n_rows, uint32_t n_cols
                               const float* centroid_thresholds, uint32_t n_thresholds, float* bpp,
                               float* col_paired, uint8_t* structs, uint32_t* n_pairs,
                               float* expect_accuracy, float* log_partition, uint32_t* row_len);
+
+/* ------------------------------------------------------------------------- */
+/* RNA-RNA duplex folding (the RNAduplex / RNAhybrid / RNAplex question: where a short RNA binds a
+ * long one, and how strongly): partition function, pair probabilities and best duplex of two
+ * strands, for a batch of strand PAIRS on the device.
+ *
+ * The model.  Strands A (nA bases) and B (nB bases), both 5'->3', base codes 0..3.  A duplex is a
+ * non-empty chain of intermolecular pairs (i_1, j_1), ..., (i_m, j_m), i in A, j in B, with
+ * i_1 < i_2 < ... < i_m and j_1 > j_2 > ... > j_m, every pair canonical, and for consecutive pairs
+ * a = i_{x+1} - i_x - 1, b = j_x - j_{x+1} - 1 with a + b <= RNAMC_MAX_2LOOP_LEN.  No intramolecular
+ * pairs.  With S = A || B (B's index j at nA + j) and R = B || A, the log weight of a duplex is
+ *   outer end   accessible(S, nA + nB, i_1, nA + j_1): reads A[i_1 - 1] and B[j_1 + 1] where they
+ *               exist; under CONTRAfold it includes basepair_scores of the first pair
+ *   + one 2-loop score twoloop(S, i_x, nA + j_x, i_{x+1}, nA + j_{x+1}) per consecutive pair (the
+ *               scores of the folding entries: they read only bases between the two pairs)
+ *   + inner end, at the pair next to the strand break: Turner accessible(R, nA + nB, j_m, nB + i_m);
+ *               CONTRAfold the junction score of that call alone (helix_close and the two dangles),
+ *               i.e. the same minus that pair's basepair_scores, which the chain has counted already.
+ *               Reads B[j_m - 1] and A[i_m + 1] where they exist.
+ * No constant initiation term is added (a caller adds their own to ln Z and to scores);
+ * allows_short_hairpins, constraints and span limits do not apply.
+ *   inside     F(i,j) = lse(inner_end(i,j), lse over k > i, l < j, a + b <= 30 of twoloop(i,j,k,l) + F(k,l)),
+ *              -inf where (A[i], B[j]) is not canonical
+ *   ln Z       lse over i, j of outer_end(i,j) + F(i,j)
+ *   outside    G(k,l) = lse(outer_end(k,l), lse over i < k, j > l, a + b <= 30 of G(i,j) + twoloop(i,j,k,l))
+ *   P(i,j)     exp(F + G - ln Z);   pa[i] = sum_j P(i,j);   pb[j] = sum_i P(i,j)
+ *   best       the same F under (max, +), then an argmax traceback: the start pair is the smallest i,
+ *              then the smallest j, among the maxima of outer_end + F; at a cell the inner end is tried
+ *              first, then (a ascending, b ascending), and the first maximal candidate wins
+ * The sums are order-free sums with the maximum taken out: loop scores are f32, every term's
+ * exponential is one hardware exp2 of its f32 distance to the running maximum, the closing logarithm
+ * one hardware log2; the log-domain values F, G and ln Z themselves are carried in f64 (a long helix
+ * reaches hundreds of nats, where an f32 ulp per cell would reach the probabilities).  The order
+ * per cell is FIXED, (a, b) ascending; ln Z is a fixed-shape reduction and pa / pb are sequential
+ * sums in f64 rounded once, so every output bit depends on the tables, the two strands and the
+ * model alone: not on the other pairs of the batch, their order, the chunking ("group_ws_bytes"),
+ * the direction the sweep steps in, or the number of devices.  The max-plus sweep is f32.
+ *
+ *   bases, offsets   n_seqs plain records (no pseudo bases), as rnamc_bpp_batch
+ *   pair_a / pair_b  n_pairs indices into the records: pair p folds A = pair_a[p] with B = pair_b[p]
+ *   match_probs      per pair nA x nB f32, row-major, at match_probs + out_offsets[p]
+ *   bound_a/bound_b  pa (nA f32) at bound_a + bound_offsets[p], pb (nB f32) at bound_b +
+ *                    bound_offsets[p] + nA: ONE prefix array of nA + nB entries per pair for both
+ *   log_partition    n_pairs f32
+ *   structs          nA + nB bytes per pair at structs + struct_offsets[p]: A's bases '(' or '.', then
+ *                    B's bases ')' or '.'
+ *   best_scores      n_pairs f32: the max-plus value
+ * Every output may be NULL and is then neither computed nor copied (a target scan passes
+ * match_probs = NULL: no nA x nB matrix leaves the device; with structs and best_scores both NULL
+ * the max-plus sweep is skipped).  match_probs needs out_offsets, bound_a / bound_b need
+ * bound_offsets, structs needs struct_offsets.
+ * A pair of strands without a canonical intermolecular pair: ln Z = -inf, probabilities 0, an
+ * all-dots structure, best score -inf, status RNAMC_OK.
+ * F and G (nA x nB f64 each) and the max-plus F (nA x nB f32) live in the context's workspace, each
+ * only when an output needs it; pairs are chunked so that a chunk fits "group_ws_bytes"; a single
+ * pair that cannot fit fails with RNAMC_ERR_OOM (and a message in rnamc_last_error) before anything
+ * is launched.
+ * RNAMC_ERR_INVALID_ARG for a NULL ctx / pool / offsets / pair list, a pair index >= n_seqs, an
+ * output without its offsets; RNAMC_ERR_EMPTY_SEQ / RNAMC_ERR_INVALID_BASE / RNAMC_ERR_SEQ_TOO_LONG
+ * for a bad record; all before any device work.  n_pairs == 0 is RNAMC_OK. */
+int rnamc_duplex_batch(rnamc_ctx* ctx, uint32_t n_seqs, const uint8_t* bases, const uint64_t* offsets,
+                       uint32_t n_pairs, const uint32_t* pair_a, const uint32_t* pair_b,
+                       int uses_contra_model, float* match_probs, const uint64_t* out_offsets,
+                       float* bound_a, float* bound_b, const uint64_t* bound_offsets,
+                       float* log_partition, uint8_t* structs, const uint64_t* struct_offsets,
+                       float* best_scores);
+/* The same over the pool's devices: the pair list is cut into contiguous bands of equal total
+ * nA * nB, every context gets the records its band names and writes straight into the caller's
+ * arrays: bit-identical to the single-context entry. */
+int rnamc_duplex_batch_multi(rnamc_pool* pool, uint32_t n_seqs, const uint8_t* bases,
+                             const uint64_t* offsets, uint32_t n_pairs, const uint32_t* pair_a,
+                             const uint32_t* pair_b, int uses_contra_model, float* match_probs,
+                             const uint64_t* out_offsets, float* bound_a, float* bound_b,
+                             const uint64_t* bound_offsets, float* log_partition, uint8_t* structs,
+                             const uint64_t* struct_offsets, float* best_scores);
+/* Log weight of ONE duplex (host only, no device): the sum of the three parts above in f64 over the
+ * f32 loop scores (the CONTRAfold inner end as accessible(R, ...) minus basepair_scores, both in
+ * f64).  chain_i / chain_j: the n_chain pairs, outer end first.  -inf (status OK) for a well-formed
+ * chain outside the model (a non-canonical pair, a + b > 30); RNAMC_ERR_INVALID_ARG for an empty or
+ * non-monotone chain or an index out of range; RNAMC_ERR_EMPTY_SEQ / RNAMC_ERR_INVALID_BASE for a
+ * bad strand. */
+int rnamc_duplex_score(const rnamc_params* params, const uint8_t* a, uint32_t n_a, const uint8_t* b,
+                       uint32_t n_b, uint32_t n_chain, const uint32_t* chain_i, const uint32_t* chain_j,
+                       int uses_contra_model, double* log_weight);
 
 #ifdef __cplusplus
 }

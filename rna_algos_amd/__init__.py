@@ -6,4 +6,4 @@ submodule that needs it raises ImportError when the library is not built.
 """
 from . import _lib  # noqa: F401
 
-__all__ = ["utils", "mccaskill_algo", "centroid_fold"]
+__all__ = ["utils", "mccaskill_algo", "centroid_fold", "duplex"]

@@ -38,6 +38,7 @@ SYMBOLS = [
     "rnamc_mutant_plan", "rnamc_mutant_scan", "rnamc_mutant_scan_multi",
     "rnamc_bpp_alignment", "rnamc_bpp_alignment_multi",
     "rnamc_context_profile_batch", "rnamc_context_profile_batch_multi", "rnamc_context_profile_stats",
+    "rnamc_duplex_batch", "rnamc_duplex_batch_multi", "rnamc_duplex_score",
 ]
 
 
@@ -209,6 +210,14 @@ def lib():
                                               vp, vp]
     L.rnamc_context_profile_batch_multi.argtypes = L.rnamc_context_profile_batch.argtypes
     L.rnamc_context_profile_stats.argtypes = [vp, u64p, C.POINTER(C.c_double)]
+    # (ctx or pool, n_seqs, bases, offsets, n_pairs, pair_a, pair_b, contra, match_probs, out_offsets,
+    # bound_a, bound_b, bound_offsets, log_partition, structs, struct_offsets, best_scores)
+    L.rnamc_duplex_batch.argtypes = [vp, C.c_uint32, vp, vp, C.c_uint32, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp,
+                                     vp, vp, vp]
+    L.rnamc_duplex_batch_multi.argtypes = L.rnamc_duplex_batch.argtypes
+    # (params, a, n_a, b, n_b, n_chain, chain_i, chain_j, contra, log_weight)
+    L.rnamc_duplex_score.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, vp, vp, C.c_int,
+                                     C.POINTER(C.c_double)]
     _lib = L
     return L
 

@@ -346,6 +346,12 @@ struct rnamc_ctx {
   rnamc::EventRing cx_events;  // profiling: a pair around every group's context kernels
   uint64_t cx_launches = 0;    // rnamc_context_profile_stats: of the last call (BatchPlan::begin resets them)
   double cx_ms = 0.0;
+  // rnamc_duplex_batch (grow-only): a chunk's pair descriptors and per-pair results, its staged
+  // probabilities (match, then bound) and structure bytes
+  rnamc::DevBuf<rnamc::DuplexPair> dx_pairs;
+  rnamc::DevBuf<rnamc::DuplexRes> dx_res;
+  rnamc::DevBuf<float> dx_out;
+  rnamc::DevBuf<uint8_t> dx_structs;
 };
 
 namespace rnamc {

@@ -260,6 +260,50 @@ void launch_context_save(const ContextBatch& b, uint32_t n_items, uint32_t max_n
 uint32_t launch_context_profile(const ContextBatch& b, bool contra, uint32_t n_items, uint32_t max_n,
                                 hipStream_t st);
 
+// RNA-RNA duplex folding (rnamc_duplex.hip): one pair of strands A, B.  Its
+// matrices F (inside) and G (outside), nA x nB f64 each (at even float offsets of the workspace), and
+// M (max-plus inside), nA x nB f32, are stored LINE-major
+// in the direction the chunk steps in: stepping along A (by_col = 0) cell (i, j) sits at
+// [i * nB + j], stepping along B (by_col = 1) at [j * nA + i] -- a step's lanes read and write
+// consecutive floats either way.
+struct DuplexPair {
+  uint64_t a_off, b_off;  // offsets of the two strands in the bases buffer
+  uint64_t f_off, g_off, m_off;  // float offsets of the three matrices in the workspace (unused ones: 0)
+  uint64_t prob_off;      // float offset of the nA x nB probabilities in `probs` (row-major)
+  uint64_t bound_off;     // float offset of the nA + nB bound probabilities in `bound`
+  uint64_t struct_off;    // byte offset of the nA + nB structure bytes in `structs`
+  uint32_t na, nb;
+};
+struct DuplexRes {
+  double log_z;                // ln Z
+  float best;                  // max over the cells of outer_end + M
+  uint32_t start_i, start_j;   // the cell of `best`: smallest i, then smallest j (0xffffffff: none)
+  uint32_t pad_;
+};
+struct DuplexChunk {
+  const DuplexPair* pairs;  // device
+  const uint8_t* bases;
+  float* ws;
+  const rnamc_params* params;
+  DuplexRes* res;           // [pair]
+  float* probs;             // may be null
+  float* bound;             // may be null
+  uint8_t* structs;         // may be null
+  uint32_t n_pairs;         // at most 65535
+  uint32_t by_col;          // 0: steps along A, 1: steps along B
+  uint32_t contra;
+};
+// One step of a sweep: line s of every pair of the chunk in the sweep's own direction (a pair with
+// fewer lines idles).  what: 0 inside (F), 1 outside (G), 2 max-plus inside (M).  max_lane: the
+// longest line of the chunk.
+void launch_duplex_step(const DuplexChunk& c, int what, uint32_t step, uint32_t max_lane, hipStream_t st);
+// ln Z (what = 0, from F) or best score and start cell (what = 2, from M): one workgroup per pair
+void launch_duplex_reduce(const DuplexChunk& c, int what, hipStream_t st);
+// match probabilities (c.probs) and / or bound probabilities (c.bound) from F, G and ln Z
+void launch_duplex_probs(const DuplexChunk& c, uint64_t max_cells, uint32_t max_bases, hipStream_t st);
+// argmax traceback from the start cell: the nA + nB structure bytes of every pair
+void launch_duplex_trace(const DuplexChunk& c, hipStream_t st);
+
 // ---- tree-order summation mode (rnamc_tree.hip) ----
 // Dense n x n matrices with row stride ld (>= n + 32, a multiple of 32 floats), msz floats
 // each; "row" = [i * ld + j], "col" = [j * ld + i].  The outside sweep reuses four slots.

@@ -141,6 +141,21 @@ int mutant_scan_core(rnamc_ctx* c, const uint8_t* bases, uint32_t n, const char*
                      uint64_t count, float* log_partition, int64_t* pair_dist2_q, float* max_dp, uint32_t* max_i,
                      uint32_t* max_j, float* paired_prob, float* wt_log_partition, float* wt_paired_prob);
 
+// rnamc_duplex_batch behind its two entries (rnamc_entries_duplex.cpp).
+// every check of the entry that needs no context: pointers, outputs and their offsets, the records,
+// the pair indices
+int duplex_batch_check(uint32_t n_seqs, const uint8_t* bases, const uint64_t* offsets, uint32_t n_pairs,
+                       const uint32_t* pair_a, const uint32_t* pair_b, const float* match_probs,
+                       const uint64_t* out_offsets, const float* bound_a, const float* bound_b,
+                       const uint64_t* bound_offsets, const uint8_t* structs, const uint64_t* struct_offsets);
+// pairs [first, first + count) of the caller's list on one context: only the records they name are
+// uploaded; every output is the call's whole array, written at the caller's offsets and pair indices
+int duplex_batch_core(rnamc_ctx* c, const uint8_t* bases, const uint64_t* offsets, uint32_t first,
+                      uint32_t count, const uint32_t* pair_a, const uint32_t* pair_b, int uses_contra_model,
+                      float* match_probs, const uint64_t* out_offsets, float* bound_a, float* bound_b,
+                      const uint64_t* bound_offsets, float* log_partition, uint8_t* structs,
+                      const uint64_t* struct_offsets, float* best_scores);
+
 // DP matrices of one sequence inside the workspace.  Every matrix is a packed
 // upper triangle of n(n+1)/2 f32 (padded to a multiple of 64 floats):
 //  - "diag-major": cell (i,j) at  d*n - d(d-1)/2 + i  with d = j-i.  A lane that

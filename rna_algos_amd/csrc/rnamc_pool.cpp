@@ -375,4 +375,56 @@ int rnamc_mutant_scan_multi(rnamc_pool* p, const uint8_t* bases, uint32_t n, con
   });
 }
 
+// The pair list is cut into contiguous bands of equal total cost nA * nB (a pair's sweeps visit every
+// cell a fixed number of times): cut k lies at the first pair where the running cost reaches
+// k / n_shards of the total, no band empty while there are pairs to give.  Every context uploads the
+// records its band names and writes its pairs straight into the caller's arrays; every output of a
+// pair is a function of the pair alone: the bits of the single-context entry.
+int rnamc_duplex_batch_multi(rnamc_pool* p, uint32_t n_seqs, const uint8_t* bases, const uint64_t* offsets,
+                             uint32_t n_pairs, const uint32_t* pair_a, const uint32_t* pair_b,
+                             int uses_contra_model, float* match_probs, const uint64_t* out_offsets,
+                             float* bound_a, float* bound_b, const uint64_t* bound_offsets, float* log_partition,
+                             uint8_t* structs, const uint64_t* struct_offsets, float* best_scores) {
+  const char* who = "rnamc_duplex_batch_multi";
+  if (!p) return RNAMC_ERR_INVALID_ARG;
+  if (int rc = duplex_batch_check(n_seqs, bases, offsets, n_pairs, pair_a, pair_b, match_probs, out_offsets,
+                                  bound_a, bound_b, bound_offsets, structs, struct_offsets))
+    return rc;
+  if (p->ctxs.empty()) return RNAMC_ERR_INVALID_ARG;
+  if (n_pairs == 0) return RNAMC_OK;
+  std::lock_guard<std::mutex> lock(p->mu);
+  const uint32_t n_shards = std::min(p->size(), n_pairs);
+  std::vector<ListBand> bands;
+  try {  // nothing may throw across the C boundary
+    std::vector<double> csum(n_pairs);
+    double run = 0.0;
+    for (uint32_t x = 0; x < n_pairs; x++) {
+      run += static_cast<double>(offsets[pair_a[x] + 1] - offsets[pair_a[x]]) *
+             static_cast<double>(offsets[pair_b[x] + 1] - offsets[pair_b[x]]);
+      csum[x] = run;
+    }
+    bands.assign(n_shards, ListBand());
+    uint32_t lo = 0;
+    for (uint32_t k = 0; k < n_shards; k++) {
+      uint32_t hi = n_pairs;
+      if (k + 1 < n_shards) {
+        hi = static_cast<uint32_t>(std::lower_bound(csum.begin(), csum.end(), run * (k + 1.0) / n_shards) -
+                                   csum.begin());
+        hi = std::min(std::max(hi, lo + 1u), n_pairs - (n_shards - 1u - k));
+      }
+      bands[k].first = lo;
+      bands[k].count = hi - lo;
+      lo = hi;
+    }
+  } catch (const std::exception&) {
+    return no_host_memory(who);
+  }
+  return run_shards(who, n_shards, [&](uint32_t k) {
+    return duplex_batch_core(p->ctxs[k], bases, offsets, static_cast<uint32_t>(bands[k].first),
+                             static_cast<uint32_t>(bands[k].count), pair_a, pair_b, uses_contra_model, match_probs,
+                             out_offsets, bound_a, bound_b, bound_offsets, log_partition, structs, struct_offsets,
+                             best_scores);
+  });
+}
+
 }  // extern "C"

@@ -132,14 +132,19 @@ struct Turner {
 
   // get_accessible_score, src/utils.rs:384-411, uses_sentinel_bases = false
   RNAMC_HD float accessible(const uint8_t* s, uint32_t n, uint32_t i, uint32_t j) const {
-    const int ai = s[i], aj = s[j];
+    const bool has_prev = i > 0, has_next = j < n - 1;
+    return accessible_codes(s[i], s[j], has_prev, has_prev ? s[i - 1] : 0, has_next, has_next ? s[j + 1] : 0);
+  }
+  // the same on base codes: the pair (ai, aj), the base before ai and the base after aj where they
+  // exist (the duplex kernels hold two strands, not one sequence: rnamc_duplex.hip)
+  RNAMC_HD float accessible_codes(int ai, int aj, bool has_prev, int prev, bool has_next, int next) const {
     float sc;
-    if (i > 0 && j < n - 1) {
-      sc = t.terminal_mismatch_scores_multibranch[ai][aj][s[i - 1]][s[j + 1]];
-    } else if (i > 0) {
-      sc = t.dangling_scores_5prime[ai][aj][s[i - 1]];
-    } else if (j < n - 1) {
-      sc = t.dangling_scores_3prime[ai][aj][s[j + 1]];
+    if (has_prev && has_next) {
+      sc = t.terminal_mismatch_scores_multibranch[ai][aj][prev][next];
+    } else if (has_prev) {
+      sc = t.dangling_scores_5prime[ai][aj][prev];
+    } else if (has_next) {
+      sc = t.dangling_scores_3prime[ai][aj][next];
     } else {
       sc = 0.f;
     }
@@ -159,10 +164,13 @@ struct Contra {
   }
 
   RNAMC_HD float junction(const uint8_t* s, uint32_t n, uint32_t p0, uint32_t p1) const {
-    const int b0 = s[p0], b1 = s[p1];
-    return f.helix_close_scores[b0][b1] +
-           (p0 < n - 1 ? f.dangling_scores_left[b0][b1][s[p0 + 1]] : 0.f) +
-           (p1 > 0 ? f.dangling_scores_right[b0][b1][s[p1 - 1]] : 0.f);
+    const bool has_next = p0 < n - 1, has_prev = p1 > 0;
+    return junction_codes(s[p0], s[p1], has_next, has_next ? s[p0 + 1] : 0, has_prev, has_prev ? s[p1 - 1] : 0);
+  }
+  // the same on base codes: `next` follows b0, `prev` precedes b1, where they exist
+  RNAMC_HD float junction_codes(int b0, int b1, bool has_next, int next, bool has_prev, int prev) const {
+    return f.helix_close_scores[b0][b1] + (has_next ? f.dangling_scores_left[b0][b1][next] : 0.f) +
+           (has_prev ? f.dangling_scores_right[b0][b1][prev] : 0.f);
   }
 
   RNAMC_HD float hairpin(const uint8_t* s, uint32_t /*n*/, uint32_t i, uint32_t j) const {
