@@ -43,8 +43,6 @@ void launch_inside_zr2(const DeviceBatch& b, uint32_t d, uint32_t max_n, uint32_
 // last (multibranch) term of the parked pair blocks of diagonals d0 .. d0+nd-1
 void launch_pair_tail(const DeviceBatch& b, bool contra, uint32_t d0, uint32_t nd, uint32_t max_n,
                       uint32_t nseq, uint32_t block, hipStream_t st);
-// true when the folds of diagonal d run in the latency form (launch too small to fill the chip)
-bool inside_is_split(uint32_t d, uint32_t max_n, uint32_t nseq);
 // roles: 7 = all three roles in one kernel; 5 = probs_multibranch + pair head; 2 = pair tail;
 // 4 = pair head alone
 void launch_outside(const DeviceBatch& b, bool contra, uint32_t d, uint32_t max_n, uint32_t nseq,

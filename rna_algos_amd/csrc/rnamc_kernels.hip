@@ -41,6 +41,7 @@
 #include <type_traits>
 
 #include "rnamc_device.h"
+#include "rnamc_schedule.h"
 #include "rnamc_scoring.h"
 
 namespace rnamc {
@@ -1843,11 +1844,6 @@ void launch_pair_tail(const DeviceBatch& b, bool contra, uint32_t d0, uint32_t n
   } else {
     hipLaunchKernelGGL(k_pair_tail<false>, g, dim3(block), 0, st, b, d0, bd, nseq);
   }
-}
-
-bool inside_is_split(uint32_t d, uint32_t max_n, uint32_t nseq) {
-  const uint32_t cells_s = d < max_n ? max_n - d : 0;
-  return static_cast<uint64_t>(cells_s) * nseq < 64ull * 1024ull;
 }
 
 // launch of diagonal d: probs_multibranch (do_mb) and multibranch half of the pair
