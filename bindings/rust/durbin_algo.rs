@@ -34,6 +34,9 @@ extern "C" {
   fn rnamc_params_new(init_val: f32, out: *mut c_void) -> c_int;
   fn rnamc_ctx_create(params: *const c_void, device: c_int, workspace_bytes: u64, out: *mut *mut RnamcCtx) -> c_int;
   fn rnamc_durbin_batch(ctx: *mut RnamcCtx, scores: *const AlignScoresC, n_seqs: u32, bases: *const u8, offsets: *const u64, n_pairs: u32, pair_a: *const u32, pair_b: *const u32, match_probs: *mut f32, out_offsets: *const u64) -> c_int;
+  // pairwise alignment off the device-resident ProbMats
+  fn rnamc_match_align(probs: *const f32, n1: u32, n2: u32, gamma: f32, mate: *mut c_int, n_matched: *mut u32, expect_accuracy: *mut f32) -> c_int;
+  fn rnamc_durbin_align_batch(ctx: *mut RnamcCtx, scores: *const AlignScoresC, n_seqs: u32, bases: *const u8, offsets: *const u64, n_pairs: u32, pair_a: *const u32, pair_b: *const u32, min_prob: f32, gammas: *const f32, n_gammas: u32, match_i: *mut u32, match_j: *mut u32, match_prob: *mut f32, cap: u64, list_start: *mut u64, list_count: *mut u64, list_total: *mut u64, mate: *mut c_int, mate_offsets: *const u64, n_matched: *mut u32, expect_accuracy: *mut f32, matched: *mut f32, matched_offsets: *const u64, match_probs: *mut f32, out_offsets: *const u64) -> c_int;
 }
 
 fn check(status: c_int, what: &str) {

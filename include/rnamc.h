@@ -45,7 +45,8 @@ extern "C" {
  *    rnamc_bpp_windowed_multi, rnamc_mutant_plan, rnamc_mutant_scan, rnamc_mutant_scan_multi,
  *    rnamc_bpp_alignment, rnamc_bpp_alignment_multi, rnamc_context_profile_batch,
  *    rnamc_context_profile_batch_multi, rnamc_context_profile_stats, rnamc_duplex_batch,
- *    rnamc_duplex_batch_multi, rnamc_duplex_score */
+ *    rnamc_duplex_batch_multi, rnamc_duplex_score, rnamc_match_align, rnamc_match_align_mats,
+ *    rnamc_durbin_align_batch */
 #define RNAMC_ABI_VERSION 3u
 
 /* Compile-time limits.  In the reference these are constants of rna-ss-params
@@ -655,6 +656,76 @@ int rnamc_durbin_batch(rnamc_ctx* ctx, const rnamc_align_scores* scores, uint32_
                        const uint8_t* bases, const uint64_t* offsets, uint32_t n_pairs,
                        const uint32_t* pair_a, const uint32_t* pair_b, float* match_probs,
                        const uint64_t* out_offsets);
+
+/* ------------------------------------------------------------------------- */
+/* Pairwise alignment off match-probability matrices: thresholded sparse
+ * match probabilities, per-base marginals and gamma-centroid (maximum expected accuracy)
+ * alignments, all made on the device while the matrices are there.
+ *
+ * The estimator, with the scoring convention of centroid_fold (src/centroid_fold.rs:49-50), for a
+ * ProbMat P of n1 x n2 (border rows and columns: the pseudo bases), L1 = n1 - 2, L2 = n2 - 2:
+ *     M[0][j] = M[i][0] = +0
+ *     M[i][j] = max(M[i-1][j], M[i][j-1], (M[i-1][j-1] + gamma * P[i][j]) - 1)    1 <= i <= L1, 1 <= j <= L2
+ * in f32; the match candidate is one rounded multiply, one rounded add and one rounded subtract, in
+ * that order, never fused.  The traceback starts at (L1, L2) and runs while i > 0 and j > 0, with
+ * exact float equality in this order: M[i][j] == M[i-1][j] -> i--; else M[i][j] == M[i][j-1] ->
+ * j--; else the match (i, j) is recorded and i--, j--.
+ *   mate             n1 values: mate[i] = the column matched with row i, or -1 (both border rows: -1)
+ *   n_matched        the number of matches;  expect_accuracy  M[L1][L2] (may be NULL)
+ * Host only, no device: the definition the two entries below reproduce bit for bit. */
+int rnamc_match_align(const float* probs, uint32_t n1, uint32_t n2, float gamma, int* mate,
+                      uint32_t* n_matched, float* expect_accuracy);
+
+/* The stage over the caller's dense matrices (callers that transform the probabilities first: a
+ * consistency transformation, an average).  Matrix m is n1[m] x n2[m] f32, row-major, at
+ * probs + prob_offsets[m]; n1[m], n2[m] >= 2.
+ *   min_prob      finite and >= 0.  An interior cell (i, j), 1 <= i <= L1, 1 <= j <= L2, is LISTED when
+ *                 p > 0 and p >= min_prob (f32 comparisons); i and j are matrix coordinates.
+ *   gammas / n_gammas   0 .. 64 finite gammas shared by all matrices; 0: lists and marginals only
+ *   match_i, match_j, match_prob   parallel arrays of `cap` entries; all three or none (none: the call
+ *                 only counts).  Matrix m's list is entries list_start[m] .. + list_count[m] - 1, in
+ *                 row-major order (i ascending, then j ascending), match_prob with the bits of the dense
+ *                 cell.  Lists of different matrices never overlap; where a list sits is unspecified.
+ *   list_start, list_count   n_mats u64 (required with the three arrays; list_count may be given alone)
+ *   list_total    never NULL: the number of listed cells of all matrices.  A capacity too small gives
+ *                 RNAMC_ERR_INVALID_ARG with list_count and *list_total set (call again with room).
+ *   mate          per matrix n_gammas rows of n1[m] values at mate + mate_offsets[m], row g at + g * n1[m]
+ *   n_matched, expect_accuracy   n_mats * n_gammas values, [m * n_gammas + g]
+ *   matched       per matrix n1[m] + n2[m] f32 at matched + matched_offsets[m]: row_matched[i] = the sum
+ *                 of P[i][j] over j = 1 .. L2 ascending, one rounded f32 add each from +0, then
+ *                 col_matched[j] likewise over i (the probability that a base is aligned to anything;
+ *                 borders 0, not clamped)
+ * Every output pointer may be NULL except list_total.  For each (m, g) mate, n_matched and
+ * expect_accuracy are exactly what rnamc_match_align returns.  Matrices run in chunks within
+ * "group_ws_bytes" (at most 65535 a chunk); results do not depend on the chunks or on the other
+ * matrices.  Bad arguments fail before any device work. */
+int rnamc_match_align_mats(rnamc_ctx* ctx, uint32_t n_mats, const uint32_t* n1, const uint32_t* n2,
+                           const float* probs, const uint64_t* prob_offsets, float min_prob,
+                           const float* gammas, uint32_t n_gammas, uint32_t* match_i,
+                           uint32_t* match_j, float* match_prob, uint64_t cap,
+                           uint64_t* list_start, uint64_t* list_count, uint64_t* list_total,
+                           int* mate, const uint64_t* mate_offsets, uint32_t* n_matched,
+                           float* expect_accuracy, float* matched,
+                           const uint64_t* matched_offsets);
+
+/* rnamc_durbin_batch followed by that stage off each chunk's device-resident ProbMats: what the
+ * callers of the reference's durbin_algo binary keep of all pairs of a FASTA.  Inputs as
+ * rnamc_durbin_batch, outputs as rnamc_match_align_mats with pair p in place of matrix m
+ * (n1 = len(a), n2 = len(b), pseudo bases included).
+ *   match_probs, out_offsets   the dense ProbMats as rnamc_durbin_batch returns them (the same bits);
+ *                 both NULL = no dense matrix is copied to the host.  Both or neither.
+ * Pairs run in chunks whose pair-HMM matrices, and then the stage's in their place, fit
+ * "group_ws_bytes" (at most 65535 pairs a chunk). */
+int rnamc_durbin_align_batch(rnamc_ctx* ctx, const rnamc_align_scores* scores, uint32_t n_seqs,
+                             const uint8_t* bases, const uint64_t* offsets, uint32_t n_pairs,
+                             const uint32_t* pair_a, const uint32_t* pair_b, float min_prob,
+                             const float* gammas, uint32_t n_gammas, uint32_t* match_i,
+                             uint32_t* match_j, float* match_prob, uint64_t cap,
+                             uint64_t* list_start, uint64_t* list_count, uint64_t* list_total,
+                             int* mate, const uint64_t* mate_offsets, uint32_t* n_matched,
+                             float* expect_accuracy, float* matched,
+                             const uint64_t* matched_offsets, float* match_probs,
+                             const uint64_t* out_offsets);
 
 /* ------------------------------------------------------------------------- */
 /* Thresholded sparse pair probabilities (the reference's SparseProbMat, src/utils.rs), compacted

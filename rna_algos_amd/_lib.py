@@ -39,6 +39,7 @@ SYMBOLS = [
     "rnamc_bpp_alignment", "rnamc_bpp_alignment_multi",
     "rnamc_context_profile_batch", "rnamc_context_profile_batch_multi", "rnamc_context_profile_stats",
     "rnamc_duplex_batch", "rnamc_duplex_batch_multi", "rnamc_duplex_score",
+    "rnamc_match_align", "rnamc_match_align_mats", "rnamc_durbin_align_batch",
 ]
 
 
@@ -218,6 +219,15 @@ def lib():
     # (params, a, n_a, b, n_b, n_chain, chain_i, chain_j, contra, log_weight)
     L.rnamc_duplex_score.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, vp, vp, C.c_int,
                                      C.POINTER(C.c_double)]
+    # (probs, n1, n2, gamma, mate, n_matched, expect_accuracy)
+    L.rnamc_match_align.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_float, vp, u32p, f32p]
+    # the outputs both alignment entries end on: (min_prob, gammas, n_gammas, match_i, match_j, match_prob, cap,
+    # list_start, list_count, list_total, mate, mate_offsets, n_matched, expect_accuracy, matched, matched_offsets)
+    match_out = [C.c_float, vp, C.c_uint32, vp, vp, vp, C.c_uint64, vp, vp, u64p, vp, vp, vp, vp, vp, vp]
+    # (ctx, n_mats, n1, n2, probs, prob_offsets, ...)
+    L.rnamc_match_align_mats.argtypes = [vp, C.c_uint32, vp, vp, vp, vp] + match_out
+    # (ctx, scores, n_seqs, bases, offsets, n_pairs, pair_a, pair_b, ..., match_probs, out_offsets)
+    L.rnamc_durbin_align_batch.argtypes = [vp, vp, C.c_uint32, vp, vp, C.c_uint32, vp, vp] + match_out + [vp, vp]
     _lib = L
     return L
 

@@ -170,6 +170,45 @@ void launch_sparse_fill(const SparseItem* items, uint32_t n_items, uint32_t max_
 void launch_sparse_paired(const SparseItem* items, uint32_t n_items, uint32_t max_n, const float* bpp,
                           float* paired, hipStream_t st);
 
+// pairwise alignment off device-resident match-probability matrices (rnamc_match.hip, DESIGN.md
+// section 20).  A matrix is a dense row-major n1 x n2 ProbMat (border rows / columns: the pseudo
+// bases); L1 = n1 - 2, L2 = n2 - 2.  Its part of the workspace holds, in this order, the block
+// counts of the compaction, the spilled diagonals of the fill (where L1 + 1 > kMatchDiagLds) and the
+// direction bytes of every gamma.
+constexpr uint32_t kMatchDiagLds = 1024u;  // cells of a live diagonal that stay in LDS
+struct MatchMat {
+  uint64_t p_off;      // float offset of the matrix in `probs`
+  uint64_t blk_off;    // u32 offset of its n_blocks block counts / bases in the workspace
+  uint64_t spill_off;  // float offset of its n_gammas * 3 * (L1 + 1) spilled diagonal cells
+  uint64_t dir_off;    // byte offset of its n_gammas * match_dir_bytes(n1, n2) direction bytes
+  uint64_t out_off;    // offset of its list in the chunk's staged i / j / p arrays (fill)
+  uint64_t mate_off;   // i32 offset of its n_gammas rows of n1 mates in the chunk's staged array
+  uint64_t marg_off;   // float offset of its n1 + n2 marginals in the chunk's staged array
+  uint32_t n1, n2;
+  uint32_t n_blocks;   // ceil(n1 * n2 / 256)
+  uint32_t pad;
+};
+// direction bytes of one (matrix, gamma): row s = i + j of L1 + 1 bytes, for s = 0 .. L1 + L2
+__host__ __device__ inline uint64_t match_dir_bytes(uint32_t n1, uint32_t n2) {
+  const uint64_t l1 = n1 - 2u, l2 = n2 - 2u;
+  return l1 && l2 ? (l1 + l2 + 1u) * (l1 + 1u) : 0u;
+}
+// at most 65535 matrices a launch (count, fill, marginals); max_blocks / max_side: the largest of
+// the launch's matrices
+void launch_match_count(const MatchMat* mats, uint32_t n_mats, uint32_t max_blocks, const float* probs,
+                        uint32_t* blocks, float min_prob, hipStream_t st);
+void launch_match_scan(const MatchMat* mats, uint32_t n_mats, uint32_t* blocks, uint32_t* totals, hipStream_t st);
+void launch_match_list(const MatchMat* mats, uint32_t n_mats, uint32_t max_blocks, const float* probs,
+                       const uint32_t* blocks, float min_prob, uint32_t* out_i, uint32_t* out_j, float* out_p,
+                       hipStream_t st);
+void launch_match_marginals(const MatchMat* mats, uint32_t n_mats, uint32_t max_side, const float* probs,
+                            float* matched, hipStream_t st);
+// fill and traceback of every (matrix, gamma): one workgroup per item, item = matrix * n_gammas + g
+// (any number of items); n_matched and accuracy are indexed by item
+void launch_match_align(const MatchMat* mats, uint32_t n_mats, const float* probs, const float* gammas,
+                        uint32_t n_gammas, float* ws, int32_t* mate, uint32_t* n_matched, float* accuracy,
+                        hipStream_t st);
+
 // windowed local folding (rnamc_window.hip): the triangles of a group of
 // windows, all of length w, summed as integers into the band accumulators of the whole sequence
 struct WindowItem {

@@ -576,6 +576,51 @@ int rnamc_centroid_fold(const float* bpp_packed, uint32_t n, float centroid_thre
   return RNAMC_OK;
 }
 
+// The gamma-centroid alignment of one ProbMat (include/rnamc.h): the definition the device stage
+// (rnamc_match.hip) reproduces bit for bit.  The match candidate is one rounded multiply, one
+// rounded add and one rounded subtract (this file is built with -ffp-contract=off).
+int rnamc_match_align(const float* probs, uint32_t n1, uint32_t n2, float gamma, int* mate,
+                      uint32_t* n_matched, float* expect_accuracy) {
+  if (!probs || !mate || !n_matched || n1 < 2 || n2 < 2) return RNAMC_ERR_INVALID_ARG;
+  if (n1 > RNAMC_MAX_SEQ_LEN + 2ull || n2 > RNAMC_MAX_SEQ_LEN + 2ull) return RNAMC_ERR_SEQ_TOO_LONG;
+  const size_t l1 = n1 - 2, l2 = n2 - 2, w = l2 + 1;
+  std::vector<float> acc;
+  try {
+    acc.assign((l1 + 1) * w, 0.f);
+  } catch (...) {
+    return RNAMC_ERR_OOM;
+  }
+  auto M = [&](size_t i, size_t j) -> float& { return acc[i * w + j]; };
+  for (size_t i = 1; i <= l1; i++)
+    for (size_t j = 1; j <= l2; j++) {
+      float best = M(i - 1, j);
+      if (M(i, j - 1) > best) best = M(i, j - 1);
+      const float gp = gamma * probs[i * n2 + j];
+      const float sum = M(i - 1, j - 1) + gp;
+      const float cand = sum - 1.f;
+      if (cand > best) best = cand;
+      M(i, j) = best;
+    }
+  for (uint32_t i = 0; i < n1; i++) mate[i] = -1;
+  uint32_t count = 0;
+  size_t i = l1, j = l2;
+  while (i > 0 && j > 0) {
+    if (M(i, j) == M(i - 1, j)) {
+      i--;
+    } else if (M(i, j) == M(i, j - 1)) {
+      j--;
+    } else {
+      mate[i] = static_cast<int>(j);
+      count++;
+      i--;
+      j--;
+    }
+  }
+  *n_matched = count;
+  if (expect_accuracy) *expect_accuracy = M(l1, l2);
+  return RNAMC_OK;
+}
+
 // AlignScores::new (src/durbin_algo.rs:26-40)
 int rnamc_align_scores_new(float init_val, rnamc_align_scores* out) {
   if (!out) return RNAMC_ERR_INVALID_ARG;
