@@ -622,7 +622,19 @@ int rnamc_centroid_fold_batch_multi(rnamc_pool* pool, uint32_t n_seqs, const uin
 /* Durbin pair-HMM nucleotide match probabilities (SURVEY.md 8f-4;
  * reference: src/durbin_algo.rs:73-242, constants src/compiled_align_scores.rs). */
 
-/* AlignScores (src/durbin_algo.rs:4-14). */
+/* AlignScores (src/durbin_algo.rs:4-14).  The model they parameterise is stated in
+ * tests/durbin_ref.py; insert_switch_score is a field that no term reads.
+ * The domain of the scores:
+ *   -inf is the way to forbid something.  The reference's logsumexp skips a term that is not
+ *   finite, so a match_scores entry at -inf gives exactly 0.0 at every cell with those two bases
+ *   and leaves the other cells the probabilities of the model without those matches.
+ *   Very negative FINITE scores are outside the domain.  The reference's logsumexp is
+ *   min + (max - min) in f32 once its two terms are more than 11.86 apart; a score far below about
+ *   -1e7 makes that difference so large that adding it back to min no longer returns max (with
+ *   -1e30 the sum comes out as 0), and the results are "probabilities" above 1, here as in the
+ *   reference.
+ *   If the scores forbid every alignment (all insert_scores at -inf and sequences of unequal
+ *   lengths, for one), the total weight is 0 and every interior cell is NaN (0 / 0). */
 typedef struct rnamc_align_scores {
   float match2match_score;
   float match2insert_score;
