@@ -392,7 +392,9 @@ int rnamc_ctx_stats(rnamc_ctx* ctx, void* out, uint64_t out_bytes, uint64_t* lib
  * of the last batch call back to the host as a dense n*n row-major f32 matrix
  * (cells outside the stored triangle = NaN).  which: 0 sums_close, 1
  * sums_accessible, 2 sums_external, 3 sums_1ormore_basepairs, 4
- * multibranch_close_scores, 5 probs_multibranch, 6 probs_multibranch2. */
+ * multibranch_close_scores, 5 probs_multibranch, 6 probs_multibranch2 (both -inf, the reference's
+ * "no entry", on the diagonals below the shortest pair span of the call's model: the outside sweep
+ * never visits them and the slot holds inside-pass data there). */
 int rnamc_debug_fetch(rnamc_ctx* ctx, uint32_t seq_idx, int which, float* out_nxn);
 /* The same for the tree-order mode: the raw workspace matrix `slot` (0 .. 37, enum TreeMat of
  * rna_algos_amd/csrc/rnamc_device.h; an internal layout, for tests only) of sequence `seq_idx` as the

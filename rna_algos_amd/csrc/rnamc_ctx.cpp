@@ -269,7 +269,11 @@ int rnamc_debug_fetch(rnamc_ctx* c, uint32_t seq_idx, int which, float* out_nxn)
       const uint64_t cm = j >> 4, cr = j & 15u;
       const uint64_t idx = row_major ? 2ull * (16ull * (cm + 1ull) * (8ull * cm + cr) + i) + (which == 6 ? 1 : 0)
                                      : (d * n - d * (d - 1ull) / 2ull + i);
-      out_nxn[static_cast<uint64_t>(i) * n + j] = packed[idx];
+      // probs_multibranch{,2} exist from the outside sweep's lowest diagonal up: below it no launch form
+      // writes the slot, which still holds the inside pass's M_ZRE / M_QM there (diagonal-major, another
+      // layout).  Those cells are reported as the reference's "no entry", not as floats of another matrix.
+      out_nxn[static_cast<uint64_t>(i) * n + j] =
+          row_major && d < c->last_dmin_out ? -std::numeric_limits<float>::infinity() : packed[idx];
     }
   return RNAMC_OK;
 }

@@ -277,6 +277,7 @@ struct rnamc_ctx {
   rnamc_batch_stats stats{};
   std::vector<rnamc::SeqDesc> descs;       // all groups, group-major
   std::vector<uint32_t> group_begin;  // prefix into descs
+  uint32_t last_dmin_out = 0;         // lowest diagonal the outside sweep of the last reference-order call wrote
   rnamc::EventRing events;            // profiling: four per group
   rnamc::EventRing kev;               // per-launch event pairs of the outside kernels (profiling)
   std::vector<uint8_t> kev_class;     // 0 main, 1 tail, 2 / 3 small; one per pair

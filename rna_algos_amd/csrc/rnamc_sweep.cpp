@@ -349,6 +349,7 @@ int run_batch(rnamc_ctx* c, uint32_t n_seqs, const uint8_t* d_bases, const uint6
     fill_active(&c->descs[gb], nseq, act);
     const GroupShape shape{gmax, nseq, contra, contra ? 0u : (RNAMC_MIN_SPAN_HAIRPIN_CLOSE - 1),
                            (contra && allows_short) ? 1u : (RNAMC_MIN_SPAN_HAIRPIN_CLOSE - 1), act.data()};
+    c->last_dmin_out = shape.dmin_out;  // (rnamc_debug_fetch)
     HipSink sink{b,        {st, c->aux_stream}, {c->ev_a.data(), c->ev_b.data()},
                  contra,   static_cast<uint32_t>(knobs.block_threads), gmax,
                  c->stats, knobs.profile >= 2,  c->kev,

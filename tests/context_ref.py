@@ -4,10 +4,13 @@ module, not a conftest.
 (a) enumerate_profile: every nested structure of the record, scored by rnamc_structure_score,
     filtered by rnamc_constraint_check, every base classified from the dot-bracket alone, in f64.
 (b) replay_profile: the sums of section 18 evaluated in f64 with numpy from the CPU oracle's f32
-    matrices (the parity gate makes those the device's bits).
+    matrices (the parity gate makes those the device's bits).  With device_arith=True the same sums
+    in the device's rounding, restated from section 18: the difference D between the two is a
+    property of the reference alone, and the GPU tests take their bound from it.
 
 Rows: 0 bulge, 1 exterior, 2 hairpin, 3 internal, 4 multibranch, 5 stem.
 """
+import functools
 import math
 
 import numpy as np
@@ -108,9 +111,155 @@ def _clean(m):
     return m
 
 
-def replay_profile(seq, contra, short, tables, mask=None):
-    """the sums of DESIGN.md section 18 in f64 from the oracle's matrices -> (6, n) f64.
-    mask: pair mask as O.bpp_masked (None: unconstrained)"""
+QUANTUM = 2.0 ** 44       # the accumulators of section 18 count units of 2^-44
+QUANTUM_CAP = 2.0 ** 45   # a term is capped at 2^45 quanta
+MIN_P = 2.0 ** -45        # closing pairs below half a quantum open no hairpin and no 2-loop on the device
+
+
+def _exp32(x):
+    """the device's exponential: the exponent, formed in f64 by the caller, rounded once to f32, and its
+    exponential taken in f32 -> f64 array of f32 values"""
+    return np.exp(np.asarray(x, np.float64).astype(np.float32)).astype(np.float64)
+
+
+def _quant(q):
+    """a term as an integer of 2^-44: to nearest, ties to even (np.rint), capped at 2^45 quanta; 0 for
+    anything not positive, NaN included -> int64 array"""
+    q = np.asarray(q, np.float64)
+    return np.where(q > 0, np.minimum(np.rint(np.where(q > 0, q, 0.0) * QUANTUM), QUANTUM_CAP), 0.0).astype(np.int64)
+
+
+@functools.lru_cache(None)
+def _slots(L):
+    """(a, b) of O.cell_scores' 2-loop list of a closing pair with min(30, j - i - 3) = L, as arrays"""
+    ab = np.array([(a, b) for a in range(L + 1) for b in range(L + 1 - a)], np.int64).reshape(-1, 2)
+    return ab[:, 0], ab[:, 1]
+
+
+def _gather(seq, contra, short, tables, mask):
+    """what both replays read: the oracle's matrices, and the hairpin and 2-loop scores of the closing
+    pairs with p > 0 alone (O.cell_scores per pair: no list of every 2-loop of the record)"""
+    seq = np.ascontiguousarray(seq, np.uint8)
+    n = len(seq)
+    packed, _, mats = O.bpp_masked(tables.ptr, seq, contra, short, mask, dump=True)
+    g = dict(zip(("qb", "qa", "z", "m1", "mbc", "pm", "pm2"), (_clean(x) for x in mats)))
+    g["m2"] = _clean(O.fold_sums_masked(tables.ptr, seq, contra, short, mask)["sums_multibranch"])
+    dense = _dense(packed, n)
+    p = np.where(dense > -0.5, dense, 0.0)
+    np.fill_diagonal(p, 0.0)
+    ii, jj = np.nonzero((p > 0) & np.isfinite(g["qb"]) & np.triu(np.ones((n, n), bool), 1))
+    hp = np.full(len(ii), np.nan)
+    pair, aa, bb, sc = [], [], [], []
+    for x, (i, j) in enumerate(zip(ii.tolist(), jj.tolist())):
+        h, _, _, tl = O.cell_scores(tables.ptr, seq, contra, short, i, j)
+        hp[x] = h
+        if len(tl):
+            a, b = _slots(min(O.MAX_2LOOP_LEN, j - i - 3))
+            assert len(a) == len(tl) == len(O.twoloop_slots(i, j))
+            pair.append(np.full(len(tl), x, np.int64))
+            aa.append(a)
+            bb.append(b)
+            sc.append(tl)
+    cat = lambda parts, dt: np.concatenate(parts).astype(dt) if parts else np.zeros(0, dt)
+    g.update(n=n, p=p, ii=ii, jj=jj, hp=hp, t_pair=cat(pair, np.int64), t_a=cat(aa, np.int64), t_b=cat(bb, np.int64),
+             t_sc=cat(sc, np.float64),
+             ce=float(tables.field("contra.external_score_unpair").ravel()[0]) if contra else 0.0,
+             cm=float(tables.field("contra.multibranch_score_unpair").ravel()[0]) if contra else 0.0)
+    return g
+
+
+def _ranges(diff, first, past, q):
+    """+q at the first base of a range, -q one past its last"""
+    np.add.at(diff, first, q)
+    np.add.at(diff, past, -q)
+
+
+def _replay(g, device_arith):
+    """the sums of section 18 over what _gather collected.  device_arith False: every term in f64.
+    True: the device's rounding as section 18 states it — every exponent formed in f64, rounded once to
+    f32, its exponential taken in f32, the product with p in f64, every term rounded to an integer of
+    2^-44 and the integers added, closing pairs with p < 2^-45 skipped, c_m inside the multibranch
+    exponents, ln V in f64.  (The device's last step, one rounding of each value to f32, is left out:
+    at most 3e-8 below 1, inside the factor the GPU tests put on D.)"""
+    n, p, qb, z, m1, m2, pm, pm2 = (g[x] for x in ("n", "p", "qb", "z", "m1", "m2", "pm", "pm2"))
+    dev = bool(device_arith)
+    ex = _exp32 if dev else np.exp
+    term = _quant if dev else (lambda q: np.asarray(q, np.float64))
+    acc = np.int64 if dev else np.float64
+    prof = np.zeros((6, n))
+    prof[STEM] = p.sum(axis=0) + p.sum(axis=1)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore", under="ignore"):
+        ii, jj, hp = g["ii"], g["jj"], g["hp"]
+        pij, qbij = p[ii, jj], qb[ii, jj]
+        live = pij >= MIN_P if dev else np.ones(len(ii), bool)
+        diff = np.zeros((6, n + 2), acc)
+        # hairpins: every pair whose hairpin the inside pass scored (NaN: it scored none)
+        sel = live & ~np.isnan(hp) & (jj - ii >= 2)
+        _ranges(diff[HAIRPIN], ii[sel] + 1, jj[sel], term(pij[sel] * ex(hp[sel] - qbij[sel])))
+        # 2-loops
+        x, a, b, sc = g["t_pair"], g["t_a"], g["t_b"], g["t_sc"]
+        i, j = ii[x], jj[x]
+        k, l = i + 1 + a, j - 1 - b
+        ok = live[x] & ~np.isnan(sc) & (a + b > 0)
+        ok[ok] = np.isfinite(qb[k[ok], l[ok]])
+        x, a, b, sc, i, j, k, l = (v[ok] for v in (x, a, b, sc, i, j, k, l))
+        q = term(pij[x] * ex(qb[k, l] + sc - qbij[x]))
+        for row, cls in ((BULGE, (a == 0) != (b == 0)), (INTERNAL, (a > 0) & (b > 0))):
+            left, right = cls & (a > 0), cls & (b > 0)
+            _ranges(diff[row], i[left] + 1, k[left], q[left])
+            _ranges(diff[row], l[right] + 1, j[right], q[right])
+        for row in (BULGE, HAIRPIN, INTERNAL):
+            prof[row] = np.cumsum(diff[row])[:n] / (QUANTUM if dev else 1.0)
+        # exterior
+        u = np.arange(n)
+        zl = np.where(u >= 1, z[0, np.maximum(u - 1, 0)], 0.0)
+        zr = np.where(u + 1 <= n - 1, z[np.minimum(u + 1, n - 1), n - 1], 0.0)
+        prof[EXTERIOR] = ex(zl + zr + g["ce"] - z[0, n - 1])
+        # multibranch
+        cm = g["cm"]
+        lw = np.where((p > 0) & np.isfinite(qb), np.log(np.where(p > 0, p, 1.0)) + g["mbc"] - qb, -np.inf)
+        lw[np.isnan(lw)] = -np.inf
+        lv = np.full(n, -np.inf)  # ln V(u, k) over k
+        for u in range(n):
+            i = np.arange(0, max(u - 1, 0))
+            k = np.arange(u + 2, n)
+            r = np.full(len(k), u + 1)  # (row u + 1 as an array: empty with k at the last base)
+            if dev:
+                t = int(_quant(_exp32(m1[i + 1, u - 1] + pm[i, u] + cm)).sum())
+                t += int(_quant(_exp32(m2[i + 1, u - 1] + pm2[i, u] + cm)).sum())
+                t += int(_quant(_exp32(m2[r, k - 1] + lv[k] + cm)).sum())
+                prof[MULTI, u] = t / QUANTUM
+            else:
+                t = np.exp(m1[i + 1, u - 1] + pm[i, u]).sum() + np.exp(m2[i + 1, u - 1] + pm2[i, u]).sum()
+                t += np.exp(m2[r, k - 1] + lv[k]).sum()
+                prof[MULTI, u] = math.exp(cm) * t
+            lv = np.logaddexp(cm + lv, lw[u, :])
+    return prof
+
+
+def replay_profile(seq, contra, short, tables, mask=None, device_arith=False):
+    """the sums of DESIGN.md section 18 from the oracle's matrices -> (6, n) f64: in f64, or with
+    device_arith in the device's rounding (see _replay).  mask: pair mask as O.bpp_masked (None:
+    unconstrained).  Walks only the closing pairs with p > 0."""
+    return _replay(_gather(seq, contra, short, tables, mask), device_arith)
+
+
+def replay_both(seq, contra, short, tables, mask=None):
+    """(f64 replay, device_arith replay) off one run of the oracle"""
+    g = _gather(seq, contra, short, tables, mask)
+    return _replay(g, False), _replay(g, True)
+
+
+def model_error(pairs):
+    """D of a list of (f64 replay, device_arith replay): the largest difference over rows 0 .. 4.  A
+    property of the reference alone."""
+    return max(float(np.abs(d[:5] - r[:5]).max()) for r, d in pairs)
+
+
+def replay_profile_dense(seq, contra, short, tables, mask=None):
+    """replay_profile as first written, off the list of EVERY 2-loop of the record (O.fold_scores:
+    hundreds of megabytes by n = 1 000).  Kept as the yardstick of the sparse walk above, which
+    tests/test_context_cpu.py holds to it within 1e-12; nothing else calls it."""
     seq = np.ascontiguousarray(seq, np.uint8)
     n = len(seq)
     packed, _, mats = O.bpp_masked(tables.ptr, seq, contra, short, mask, dump=True)

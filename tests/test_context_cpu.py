@@ -75,6 +75,50 @@ def test_replay_matches_enumeration(built, tables_name):
     print("worst", worst, "ratio to the bpp error", worst / (b / 8))
 
 
+@pytest.mark.parametrize("model", [TURNER, CONTRA, SHORT])
+def test_sparse_replay_equals_the_dense_one_and_model_error_is_within_the_gpu_bound(built, model):
+    """replay_profile walks the closing pairs with p > 0 alone; replay_profile_dense is its first form off
+    the list of every 2-loop.  Equal to 1e-12 on every input of the GPU test and of this file (another
+    order of the same f64 sums: 1.4e-14 measured).  And D, the largest |device_arith replay - f64
+    replay| over rows 0 .. 4, on the GPU test's inputs up to n = 130 stays within that test's bound of
+    four times the 6.07e-8 measured on the device: the model of the device's arithmetic and the old
+    measurement cannot drift apart unnoticed."""
+    import context_ref as R
+    import test_gpu_context as G
+    from rna_algos_amd.utils import bytes2seq
+    contra, short = model
+    inputs = [(tn, label, seq, mask) for tn, label, seq, _, mask in G.replay_inputs()]
+    for tn in ("synthetic1", "zero"):
+        inputs += [(tn, s, bytes2seq(s), None) for s in sorted({s for s, _ in FIXED})]
+        inputs += [(tn, f"splitmix({n},{seed})", O.splitmix_seq(n, seed), None) for n, seed, _ in SPLITMIX]
+    from constraint_masks import allowed_matrix
+    inputs.append(("zero", CONS, bytes2seq(SEVENTEEN), allowed_matrix(CONS, SPAN)))
+    worst, pairs = 0.0, []
+    for tn, label, seq, mask in inputs:
+        T = _tables(tn)
+        dense = R.replay_profile_dense(seq, contra, short, T, mask)
+        r, d = R.replay_both(seq, contra, short, T, mask)
+        err = float(np.abs(r - dense).max())
+        worst = max(worst, err)
+        assert err <= 1e-12, (tn, label, err)
+        if len(seq) <= 130:
+            pairs.append((r, d))
+    D = R.model_error(pairs)
+    print(model, "worst |sparse - dense| %.2e" % worst, "D %.2e" % D, "bound %.2e" % G.BOUND)
+    assert 0 < D <= G.BOUND
+
+
+def test_device_arithmetic_model_rounds_as_stated():
+    """the two primitives of device_arith: quanta to nearest with ties to even, the cap, nothing for a
+    term that is not positive; the exponent rounded to f32 before the f32 exponential"""
+    import context_ref as R
+    q = R._quant(np.array([0.5, 1.5, 2.5, 2.0 ** 46, -1.0, 0.0, np.nan]) / R.QUANTUM)
+    assert q.tolist() == [0, 2, 2, 2 ** 45, 0, 0, 0]
+    x = 1.0 + 2.0 ** -30  # rounds to 1 in f32
+    assert R._exp32(np.array([x]))[0] == float(np.exp(np.float32(1.0)))
+    assert R.MIN_P == 2.0 ** -45 and R.QUANTUM == 2.0 ** 44
+
+
 def test_every_row_carries_mass_under_the_zero_tables(built):
     """not vacuous: by the enumeration every one of the six rows reaches 0.05 at some base of the 17-mer"""
     (label, e, _, _) = cases("zero")[0]
